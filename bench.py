@@ -14,8 +14,15 @@ eigenvalues, backward, gradient all-reduce (N > 1), Adam. The dataset is residen
 before timing. --data static rebuilds the CSR of one fixed batch from edge_index every step
 instead; --data host collates on the host (PCIe-inclusive).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...      (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the line. --full adds the measurements
+that take runs of their own: `cpu_baseline` (the oracle's train step on the host cores) and the
+nested `cfg3` block (the super-node configuration measured after the headline). --dump-outputs DIR
+writes what the last timed step left with its caller (the loss, the updated parameters and buffers,
+the gradients; the prediction for --mode infer) as DIR/<name>.npy after the timed steps; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line. `roofline` is the dominant kernel: the SAGE-layer GEMM family
 (forward z = x [W_l;W_r]^T, dgrad or wgrad; 18 GEMMs of 84.6 GFLOP each per step) with the
@@ -127,9 +134,17 @@ def parse():
                          "times in one batch, eval mode, no_grad forward passes (a separate line, not the "
                          "BASELINE metric)")
     ap.add_argument("--infer-batch", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take runs of their own: the CPU baseline (oracle train "
+                         "step on the host cores) and the nested cfg3 (super-node) block of the cfg2 line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (train: loss, updated "
+                         "parameters and buffers, gradients; infer: the prediction) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed seeded sample of the elements beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-cfg3", action="store_true",
-                    help="skip the cfg3 (super-node) block the default cfg2 line nests after its own measurement")
+                    help="with --full: skip the cfg3 (super-node) block the cfg2 line nests after its own "
+                         "measurement")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--cache-graph", action="store_true", help="reuse the CSR across steps (not the default)")
     ap.add_argument("--data", default="store", choices=["static", "store", "host"],
@@ -160,7 +175,60 @@ def parse():
                     help="bgnn_set_tuning(KNOB, VALUE) before the run (A/B profiling; include/bgnn.h BGNN_TUNE_*)")
     ap.add_argument("--py-set", action="append", default=[], metavar="MODULE.ATTR=EXPR",
                     help="set a bgnn module switch before the run (A/B profiling), e.g. bgnn.fused.WSPLIT=False")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, tensors):
+    """Write name -> tensor as dirname/<name>.npy (float64 stays, everything else as float32). Beyond
+    DUMP_LIMIT_BYTES in all, every array of more than 4,096 elements keeps the same fraction of its
+    elements (flattened), chosen by a fixed seed: the same indices in every run and build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, t in tensors.items():
+        if hasattr(t, "detach"):
+            t = t.detach().cpu()
+            t = (t if t.dtype.is_floating_point and t.element_size() >= 4 else t.float()).numpy()
+        a = np.asarray(t)
+        arrs[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    frac = min(1.0, 0.9 * DUMP_LIMIT_BYTES / max(1, total))
+    for name, a in arrs.items():
+        if frac < 1.0 and a.size > 4096:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def _mesh_arrays(job):
+    """(worker of make_pool) one synthetic mesh as numpy arrays."""
+    from bgnn import synthetic
+    n, seed, super_node = job
+    d = synthetic.make_mesh_graph(n, seed, super_node=super_node)
+    return d.x.numpy(), d.edge_index.numpy(), d.edge_attr.numpy(), d.y.numpy()
+
+
+def make_pool(n, seeds, super_node):
+    """[synthetic.make_mesh_graph(n, s, super_node) for s in seeds]. The random virtual edges are drawn
+    pair by pair (85 ms a mesh), so while this process has not touched the GPU yet the meshes are
+    generated by forked workers; every mesh depends on its seed alone, the pool is the same."""
+    import multiprocessing as mp
+    import torch
+    import bgnn
+    from bgnn import synthetic
+    workers = min(16, os.cpu_count() or 1, len(seeds) // 8)
+    if workers < 2 or super_node or torch.cuda.is_initialized():
+        return [synthetic.make_mesh_graph(n, s, super_node=super_node) for s in seeds]
+    with mp.get_context("fork").Pool(workers) as pool:
+        parts = pool.map(_mesh_arrays, [(n, s, super_node) for s in seeds], chunksize=4)
+    return [bgnn.Data(x=torch.from_numpy(x), edge_index=torch.from_numpy(ei), edge_attr=torch.from_numpy(ea),
+                      y=torch.from_numpy(y)) for x, ei, ea, y in parts]
 
 
 def cpu_baseline(batch, model_state, model_name, steps):
@@ -253,6 +321,8 @@ def run_infer(args, model, dev, world, rank):
         "latency_ms_per_graph": round(elapsed / args.steps / args.infer_batch * 1e3, 5),
         "pred_checksum": float(pred.double().sum()),
     }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pred": pred})
     if rank == 0:
         def clean(o):
             if isinstance(o, dict):
@@ -301,11 +371,12 @@ def build_model(args, model_name, dev):
     return model, state0
 
 
-def measure_train(args, config, model_name, dev, world, rank, steps, warmup, heavy_timing=False):
+def measure_train(args, config, model_name, dev, world, rank, steps, warmup, heavy_timing=False, dump_dir=None):
     """Build the data (a resident GraphStore of meshes per rank), model and optimizer, run `warmup`
     untimed and `steps` timed train steps (barrier + synchronize on both sides, max over ranks).
     Returns a dict: elapsed (s), timers (bgnn.fused per-launch HIP events), batch (first batch),
-    batch_cpu, loss, lr, state0, bsz, steps, heavy (chunk + combine timing of the super rows)."""
+    batch_cpu, loss, lr, state0, bsz, steps, heavy (chunk + combine timing of the super rows).
+    dump_dir: rank 0 writes the last timed step's loss, parameters, buffers and gradients there."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -315,6 +386,21 @@ def measure_train(args, config, model_name, dev, world, rank, steps, warmup, hea
 
     bsz = synthetic.CONFIGS[config]["graphs"]
     batch_cpu = synthetic.make_config_batch(config, rank=rank)
+    pool = None
+    if args.data != "static":
+        # a pool of meshes per rank (made before this process first touches the GPU: make_pool)
+        c = synthetic.CONFIGS[config]
+        if args.epochs > 0:
+            # this rank's shard of a global dataset (graph g seeded by its global id)
+            n_global = args.dataset_graphs or args.store_graphs * world
+            gids = list(range(rank, n_global, world))
+            if len(gids) < bsz:
+                raise SystemExit(f"--epochs: the shard of rank {rank} has {len(gids)} graphs, fewer than a batch")
+            pool = make_pool(c["n"], gids, c["super_node"])
+            per_epoch = len(gids) // bsz
+            steps = args.epochs * per_epoch
+        else:
+            pool = make_pool(c["n"], [1000 * rank + g for g in range(args.store_graphs)], c["super_node"])
     batch = batch_cpu.to(dev)
     model, state0 = build_model(args, model_name, dev)
     is_ea = model_name.startswith("EA_GNN")
@@ -334,20 +420,7 @@ def measure_train(args, config, model_name, dev, world, rank, steps, warmup, hea
                 bgnn.clear_caches()
             return bgnn.train_step(model, batch, opt, crit, norm, allreduce=ar)
     else:
-        # a pool of meshes per rank, a different shuffled 16-graph batch every step
-        c = synthetic.CONFIGS[config]
-        if args.epochs > 0:
-            # this rank's shard of a global dataset (graph g seeded by its global id)
-            n_global = args.dataset_graphs or args.store_graphs * world
-            gids = list(range(rank, n_global, world))
-            if len(gids) < bsz:
-                raise SystemExit(f"--epochs: the shard of rank {rank} has {len(gids)} graphs, fewer than a batch")
-            pool = [synthetic.make_mesh_graph(c["n"], g, super_node=c["super_node"]) for g in gids]
-            per_epoch = len(gids) // bsz
-            steps = args.epochs * per_epoch
-        else:
-            pool = [synthetic.make_mesh_graph(c["n"], 1000 * rank + g, super_node=c["super_node"])
-                    for g in range(args.store_graphs)]
+        # a different shuffled 16-graph batch of the pool every step
         store = bgnn.GraphStore(pool, dev) if args.data == "store" else None
         rng = np.random.default_rng(rank)
         state = {"order": iter(()), "epoch": -1}
@@ -412,6 +485,11 @@ def measure_train(args, config, model_name, dev, world, rank, steps, warmup, hea
     res = {"elapsed": elapsed, "timers": timers, "batch": batch, "batch_cpu": batch_cpu, "loss": float(loss.item()),
            "lr": lr, "state0": state0, "bsz": bsz, "steps": steps, "heavy": heavy,
            "event_steps": len(range(0, steps, every))}
+    if dump_dir and rank == 0:
+        out = {"loss": loss}
+        out.update({"param." + k: v for k, v in model.state_dict().items()})
+        out.update({"grad." + k: p.grad for k, p in model.named_parameters() if p.grad is not None})
+        dump_outputs(dump_dir, out)
     del model, opt, store
     return res
 
@@ -633,7 +711,8 @@ def main():
         model, _ = build_model(args, args.model, dev)
         return run_infer(args, model, dev, world, rank)
 
-    m = measure_train(args, args.config, args.model, dev, world, rank, args.steps, args.warmup)
+    m = measure_train(args, args.config, args.model, dev, world, rank, args.steps, args.warmup,
+                      dump_dir=args.dump_outputs)
     m["config"] = args.config
     steps, bsz, elapsed = m["steps"], m["bsz"], m["elapsed"]
     batch = m["batch"]
@@ -717,12 +796,12 @@ def main():
             "mfma": {"achieved": round(ea_tfs, 2), "peak": ea_peak, "unit": "TFLOP/s",
                      "frac": round(ea_tfs / ea_peak, 4), "algorithmic_flop": ea_flop},
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(m["batch_cpu"], m["state0"], args.model, args.cpu_steps)
     batch_cpu = m.pop("batch_cpu")
     del m, batch, batch_cpu
-    # BASELINE configs[2] (super nodes) nested in the same line; the headline stays cfg2
-    if (args.config == "cfg2" and not args.no_cfg3 and not is_ea and args.path == "fused" and args.epochs <= 0
+    # --full: BASELINE configs[2] (super nodes) nested in the same line; the headline stays cfg2
+    if (args.full and args.config == "cfg2" and not args.no_cfg3 and not is_ea and args.path == "fused" and args.epochs <= 0
             and args.data == "store"):
         torch.cuda.empty_cache()
         out["cfg3"] = cfg3_block(args, dev, world, rank)

@@ -142,6 +142,27 @@ def run_case(BuckGNN, case):
     return name, out
 
 
+LAYOUT_VARIANTS = ["GraphSage_addAggr", "GraphSage_sumAggr", "GraphSage_meanAggr", "GraphSage_maxAggr",
+                   "GraphSage_addAggr_Shared", "EA_GNN", "EA_GNN_Shared", "GraphSAGE_MLP", "GraphSAGE_SAG",
+                   "EAGNN_SAG"]
+
+
+def write_state_dict_layout(BuckGNN, out_dir):
+    """state_dict_layout.json: "<model_name>/<hidden>" -> [[key, shape], ...] of the reference class's
+    state dict, in its order (tests/test_host.py checks bgnn.BuckGNN against it)."""
+    import json
+    layout = {}
+    for name in LAYOUT_VARIANTS:
+        for hidden in (64, 512):
+            sd = BuckGNN(16, 5, hidden_channels=hidden, num_layers=6, pooling_layer="mean", dropout_rate=0.1,
+                         model_name=name).state_dict()
+            layout[f"{name}/{hidden}"] = [[k, list(v.shape)] for k, v in sd.items()]
+    path = os.path.join(out_dir, "state_dict_layout.json")
+    with open(path, "w") as f:
+        json.dump(layout, f, separators=(",", ":"))
+    print(f"state-dict layouts of {len(layout)} models -> {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=HERE)
@@ -168,6 +189,8 @@ def main():
         total += os.path.getsize(path)
         print(f"{name}: pred={out['pred_train']} loss={float(out['loss_train']):.6f} -> {path}")
     print(f"total fixture bytes: {total}")
+    if not only:
+        write_state_dict_layout(BuckGNN, args.out)
     shim.uninstall()
     return 0
 

@@ -1,7 +1,9 @@
 """Host-side logic (CPU only): synthetic inputs, PyG-compatible containers and
 collation, the PyG shim, BuckGNN module/state-dict layout, and 'no CPU fallback'."""
+import json
 import os
 import sys
+import textwrap
 
 import numpy as np
 import pytest
@@ -11,7 +13,10 @@ import bgnn
 from bgnn import synthetic as S
 from oracle import pyg_ref as P
 
-REF = "/root/reference"
+# state-dict keys and shapes of the reference's own BuckGNN, recorded by tests/golden/make_golden.py
+LAYOUT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "state_dict_layout.json")
+with open(LAYOUT_PATH) as _f:
+    REF_LAYOUT = json.load(_f)
 
 
 def test_mesh_config_sizes_match_survey():
@@ -79,26 +84,20 @@ VARIANTS = ["GraphSage_addAggr", "GraphSage_sumAggr", "GraphSage_meanAggr", "Gra
             "GraphSage_addAggr_Shared", "EA_GNN", "EA_GNN_Shared", "GraphSAGE_MLP", "GraphSAGE_SAG", "EAGNN_SAG"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not present")
 @pytest.mark.parametrize("hidden", [64, 512])
 @pytest.mark.parametrize("name", VARIANTS)
 def test_state_dict_layout_matches_reference(name, hidden):
-    """The reference's BuckGNN (imported unchanged through bgnn's PyG shim) and bgnn.BuckGNN
-    have identical state-dict keys and shapes, so checkpoints load both ways."""
-    bgnn.install_pyg_shim(batchnorm=False, fused_model=False)
-    sys.path.insert(0, REF)
-    try:
-        from Models.BuckGNN import BuckGNN as RefBuckGNN
-    finally:
-        sys.path.remove(REF)
+    """The reference's BuckGNN (its state-dict keys, order and shapes as recorded in
+    tests/golden/state_dict_layout.json) and bgnn.BuckGNN have identical state-dict keys and
+    shapes, so checkpoints load both ways."""
     kw = dict(hidden_channels=hidden, num_layers=6, pooling_layer="mean", dropout_rate=0.1, model_name=name)
-    ref = RefBuckGNN(16, 5, **kw).state_dict()
+    ref = {k: torch.zeros(shape, dtype=torch.long if k.endswith("num_batches_tracked") else torch.float32)
+           for k, shape in REF_LAYOUT[f"{name}/{hidden}"]}
     mine = bgnn.BuckGNN(16, 5, **kw).state_dict()
     assert list(ref.keys()) == list(mine.keys())
     for k in ref:
-        assert ref[k].shape == mine[k].shape, k
+        assert ref[k].shape == mine[k].shape and ref[k].dtype == mine[k].dtype, k
     bgnn.BuckGNN(16, 5, **kw).load_state_dict(ref)
-    bgnn.uninstall_pyg_shim()
 
 
 def test_reference_defects_reproduced():
@@ -200,12 +199,51 @@ def test_pyg_shim_batchnorm_patches_and_restores():
     assert torch.nn.BatchNorm1d is orig
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference checkout")
-def test_pyg_shim_binds_fused_model_class():
-    """install_pyg_shim()'s import hook: the reference's unchanged Models/BuckGNN.py, imported the way
-    TRAIN_FINAL.py / INFERENCE.py import it, exports bgnn.BuckGNN as BuckGNN (same constructor and
-    state-dict keys as the reference class, kept as BuckGNN_reference); a module imported before the
-    shim is rebound in place; uninstall restores the reference class."""
+# A stand-in for the reference's Models/BuckGNN.py, shaped like it where the shim's import hook
+# looks: the third-party names it imports, a class BuckGNN with the reference's constructor signature
+# whose __init__ finds its own class through the module globals (two-argument super), and the
+# reference's state dict (keys, order, shapes from the recorded layout).
+STAND_IN_MODEL = textwrap.dedent('''
+    import json
+
+    import torch
+    import torch.nn as nn
+    from torch_geometric.nn import SAGEConv, SAGPooling, global_add_pool, global_max_pool, global_mean_pool
+    from torch_scatter import scatter_add, scatter_mean
+
+    with open({layout!r}) as f:
+        LAYOUT = json.load(f)
+    BUFFERS = ("running_mean", "running_var", "num_batches_tracked")
+
+
+    class BuckGNN(nn.Module):
+        def __init__(self, num_node_features, num_edge_features, hidden_channels=128, num_layers=6,
+                     pooling_layer="mean", prediction_type="buckling", use_z_coord=False, use_rotations=False,
+                     dropout_rate=0.1, model_name="GraphSAGE_MLP"):
+            super(BuckGNN, self).__init__()
+            for key, shape in LAYOUT[f"{{model_name}}/{{hidden_channels}}"]:
+                *path, leaf = key.split(".")
+                m = self
+                for name in path:
+                    if name not in m._modules:
+                        m.add_module(name, nn.Module())
+                    m = m._modules[name]
+                if leaf in BUFFERS:
+                    m.register_buffer(leaf, torch.zeros(shape, dtype=torch.long if leaf == BUFFERS[2] else torch.float32))
+                else:
+                    m.register_parameter(leaf, nn.Parameter(torch.zeros(shape)))
+''')
+
+
+def test_pyg_shim_binds_fused_model_class(tmp_path):
+    """install_pyg_shim()'s import hook: a Models/BuckGNN.py (STAND_IN_MODEL), imported the way
+    TRAIN_FINAL.py / INFERENCE.py import the reference's, exports bgnn.BuckGNN as BuckGNN (same
+    constructor and state-dict keys as the reference class, kept as BuckGNN_reference); a module imported
+    before the shim is rebound in place; uninstall restores the reference class."""
+    (tmp_path / "Models").mkdir()
+    (tmp_path / "Models" / "__init__.py").write_text("")
+    (tmp_path / "Models" / "BuckGNN.py").write_text(STAND_IN_MODEL.format(layout=LAYOUT_PATH))
+    REF = str(tmp_path)
     for k in [k for k in sys.modules if k == "Models" or k.startswith("Models.")]:
         del sys.modules[k]
     sys.path.insert(0, REF)
@@ -221,6 +259,7 @@ def test_pyg_shim_binds_fused_model_class():
                       model_name="GraphSage_addAggr_Shared")
             ours, ref = BuckGNN(16, 5, **kw), ref_cls(16, 5, **kw)
             assert list(ours.state_dict()) == list(ref.state_dict())
+            assert list(ref.state_dict()) == [k for k, _ in REF_LAYOUT["GraphSage_addAggr_Shared/64"]]
             ours.load_state_dict(ref.state_dict())   # a reference checkpoint loads unchanged (strict)
         finally:
             bgnn.uninstall_pyg_shim()

@@ -8,7 +8,8 @@
 #   tests      pytest -m gpu over ${TESTS:-tests} (PYTEST_ARGS adds arguments); assertion failures
 #              (rc 1) are reported and do not stop the later measurements
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py (the driver's line; BENCH_ARGS adds arguments)
+#   bench      python bench.py --full (the headline with the CPU baseline and the nested cfg3 block;
+#              BENCH_ARGS adds arguments)
 #   cfg3       bench.py --config cfg3
 #   max        bench.py --model GraphSage_maxAggr
 #   shared     bench.py --model GraphSage_addAggr_Shared
@@ -61,7 +62,7 @@ for s in $STEPS; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "gpurun_out/smoke_$TAG.log" 2>&1 \
         || die smoke $?
       tail -1 "gpurun_out/smoke_$TAG.log" ;;
-    bench) bench cfg2 400 ;;
+    bench) bench cfg2 400 --full ;;
     cfg3) bench cfg3 300 --config cfg3 --no-cpu-baseline ;;
     max) bench max 300 --model GraphSage_maxAggr --no-cpu-baseline ;;
     shared) bench shared 300 --model GraphSage_addAggr_Shared --no-cpu-baseline ;;
