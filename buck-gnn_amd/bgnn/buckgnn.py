@@ -200,6 +200,10 @@ class BuckGNN(nn.Module):
         # operands with f32 accumulation and bf16 storage of the per-edge activations
         # (BASELINE configs[4]; bgnn.ea.BF16_STORAGE)
         self.ea_bf16 = False
+        # GraphSAGE sum / mean models, eval mode under no_grad on the fused path: bf16 layer rows and
+        # one bf16 MFMA product per GEMM, each layer a GEMM plus one aggregation + tail kernel
+        # (fused.sage_infer_layer). Off: the f32-accurate path, as in training. (_infer_bf16_on)
+        self.infer_bf16 = False
         self._step = 0
 
     # ------------------------------------------------------------------ pooling
@@ -253,6 +257,29 @@ class BuckGNN(nn.Module):
     def _sage_fused(self, x: Tensor, aggr: str) -> bool:
         return self._fused_ok(x) and aggr in ("add", "sum", "mean", "max")
 
+    def _infer_bf16_on(self, x: Tensor, aggr: str, bns) -> bool:
+        """Whether the SAGE layer loop takes the bf16 inference path (infer_bf16): eval mode without
+        autograd on the fused path, a sum / mean aggregation, rows of whole 16-byte bf16 vectors
+        and BatchNorms with running statistics (their scale / shift are then known up front)."""
+        h = self.hidden_channels
+        return bool(self.infer_bf16 and not self.training and not torch.is_grad_enabled()
+                    and self._fused_ok(x) and aggr in ("add", "sum", "mean") and h % 8 == 0 and h <= 512
+                    and (bns is None or all(bn.track_running_stats and bn.running_mean is not None
+                                            for bn in bns)))
+
+    def _sage_loop_bf16(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, pool=None):
+        """The eval-mode SAGE layer loop on bf16 rows: per layer one bf16 GEMM and one aggregation +
+        tail kernel; the last layer writes f32 for the pooling and the decoder."""
+        L = len(convs) if convs is not None else self.num_layers
+        graph = graph_for(edge_index, x.size(0))
+        red = 1 if aggr == "mean" else 0
+        for i in range(L):
+            conv = convs[i] if convs is not None else self.shared_graphsage_block
+            coeffs = _fused.bn_eval_coeffs(bns[i]) if bns is not None else None
+            x = _fused.sage_infer_layer(x, _fused.infer_weights(conv), conv.lin_l.bias, coeffs, graph, red,
+                                        x_prev=x if 0 < i < L - 1 else None, out_f32=i == L - 1)
+        return (x, segment_reduce(x, pool, "mean")) if pool is not None else x
+
     def _foldable_encoder(self, x: Tensor) -> bool:
         """The node encoder's last Linear can be folded into the first fused SAGE layer (which
         has no skip connection): the encoder output x0 = h W^T + b feeds only that layer's
@@ -268,6 +295,8 @@ class BuckGNN(nn.Module):
         (x, mean pool of x per segment) from the last fused layer instead of x."""
         L = len(convs) if convs is not None else self.num_layers
         p = self.dropout.p
+        if x_in is None and self._infer_bf16_on(x, aggr, bns):
+            return self._sage_loop_bf16(x, edge_index, convs, bns, aggr, pool)
         if self._sage_fused(x, aggr):
             graph = graph_for(edge_index, x.size(0))
             red = {"mean": 1, "max": 2}.get(aggr, 0)
@@ -376,9 +405,12 @@ class BuckGNN(nn.Module):
         x_amax = None   # max|x| after the encoder (f16x3 operand scale of the first SAGE GEMM)
         x_in = None     # the encoder's last Linear when it is folded into the first SAGE layer
         sage = _SAGE_VARIANTS.get(name, (None, "add", None))[1] if name != "GraphSage_addAggr_Shared" else "add"
+        # the bf16 inference loop takes the encoder's f32 output: the encoder stays unfolded
+        infer = ((name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared")
+                 and self._infer_bf16_on(x, sage, self.batch_norms if name in _SAGE_VARIANTS else None))
         # (GraphSAGE_SAG folds into sage_layers_1[0]: not when that list is empty, num_layers == 1)
         if (name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"
-                or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) \
+                or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) and not infer \
                 and self._sage_fused(x, sage) and sage != "max" and self._foldable_encoder(x):
             x_in = self.node_encoder[-1]
             x, x_amax = mlp(self.node_encoder[:-1], x, return_amax=True)

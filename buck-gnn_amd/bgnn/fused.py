@@ -1405,3 +1405,73 @@ def sage_conv(x: torch.Tensor, w_l: torch.Tensor, b_l, w_r: torch.Tensor, graph:
     (SageConvFn); reduce 0 = sum/add, 1 = mean, 2 = max (aggregate-first)."""
     require_cuda(x, w_l, w_r, what="sage_conv")
     return SageConvFn.apply(x, w_l, b_l, w_r, graph, reduce)
+
+
+# ---------------------------------------------------------------------------
+# bf16 inference layer (BuckGNN.infer_bf16): eval mode only, no autograd.
+
+def infer_weights(conv) -> torch.Tensor:
+    """[W_l ; W_r] of a SAGEConv as one bf16 [2H, H] matrix (the B^T operand of the layer's
+    GEMM), built once per weight version and kept on the module: rebuilt when either weight is
+    written in place (`_version`) or replaced (storage / device)."""
+    w_l, w_r = conv.lin_l.weight, conv.lin_r.weight
+    key = (w_l._version, w_r._version, w_l.data_ptr(), w_r.data_ptr(), str(w_l.device))
+    hit = getattr(conv, "_bgnn_infer_wcat", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        wcat = torch.cat([w_l.detach(), w_r.detach()], 0).to(torch.bfloat16).contiguous()
+    conv._bgnn_infer_wcat = (key, wcat)
+    return wcat
+
+
+def bn_eval_coeffs(bn):
+    """(scale, shift) of an eval-mode BatchNorm1d from its running statistics
+    (bgnn_bn_eval_coeffs): BN(o) = o * scale + shift."""
+    H = bn.num_features
+    dev = bn.running_mean.device
+    scale = torch.empty(H, dtype=torch.float32, device=dev)
+    shift = torch.empty(H, dtype=torch.float32, device=dev)
+    _lib.call("bgnn_bn_eval_coeffs", H, _ptr(bn.weight), _ptr(bn.bias), float(bn.eps), bn.running_mean.data_ptr(),
+              bn.running_var.data_ptr(), scale.data_ptr(), shift.data_ptr(), _stream())
+    return scale, shift
+
+
+@torch.no_grad()
+def sage_infer_layer(x: torch.Tensor, w_cat: torch.Tensor, bias, bn_coeffs, graph: Graph, reduce: int,
+                     x_prev=None, out_f32: bool = False) -> torch.Tensor:
+    """One eval-mode GraphSAGE layer on bf16 rows, two launches:
+        z = x [W_l ; W_r]^T                       bf16 in, bf16 out, one MFMA product (gemm_bf16)
+        y = ReLU(BN(normalize(AGG z_l + z_r + b))) (+ x_prev)     bgnn_sage_infer_bf16
+    x: [N, H] bfloat16 (a float32 x, the encoder's output, is rounded to bf16 once); w_cat: bf16
+    [2H, H] (infer_weights); bias: f32 [H] or None; bn_coeffs: (scale, shift) f32 [H] or None;
+    reduce: 0 sum, 1 mean; x_prev: the skip input [N, H] or None. Returns y [N, H] as bfloat16, or
+    float32 with out_f32 (the last layer). No autograd."""
+    require_cuda(x, w_cat, bias, x_prev, what="sage_infer_layer")
+    N, H = x.size(0), w_cat.size(1)
+    if w_cat.dtype != torch.bfloat16 or w_cat.size(0) != 2 * H or x.size(1) != H:
+        raise ValueError("sage_infer_layer: w_cat must be bfloat16 [2H, H] and x [N, H]")
+    if H % 8 or H > 512:
+        raise ValueError(f"sage_infer_layer: needs H % 8 == 0 and H <= 512 (got {H})")
+    if reduce not in (0, 1):
+        raise ValueError("sage_infer_layer: reduce must be 0 (sum) or 1 (mean)")
+    dev = x.device
+    xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+    if xb.stride(1) != 1 or xb.stride(0) % 8:
+        xb = xb.contiguous()
+    with _timed("infer_gemm"):
+        z = gemm_bf16(xb, w_cat, trans_a=False, trans_b=True, out_bf16=True)
+    xp = None
+    if x_prev is not None:
+        xp = x_prev if x_prev.dtype == torch.bfloat16 else x_prev.to(torch.bfloat16)
+        if xp.stride(1) != 1 or xp.stride(0) % 8:
+            xp = xp.contiguous()
+    scale, shift = bn_coeffs if bn_coeffs is not None else (None, None)
+    out = torch.empty(N, H, dtype=torch.float32 if out_f32 else torch.bfloat16, device=dev)
+    n_chunks = graph.fwd.plan.n_chunks
+    part = torch.empty(n_chunks * H, dtype=torch.float32, device=dev) if n_chunks else None
+    with _timed("sage_infer"):
+        _lib.call("bgnn_sage_infer_bf16", graph.fwd.ref(), z.data_ptr(), z.stride(0), _ptr(bias), _ptr(scale),
+                  _ptr(shift), _ptr(xp), xp.stride(0) if xp is not None else 0, H, reduce, out.data_ptr(),
+                  out.stride(0), int(out_f32), _ptr(part), _stream())
+    return out

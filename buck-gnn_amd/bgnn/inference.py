@@ -19,9 +19,26 @@ from .train import EigenvalueScaler
 
 @torch.no_grad()
 def evaluate(model, batches: Iterable, normalizer: Optional[EigenvalueScaler] = None,
-             device=None) -> Dict[str, float]:
-    """Buckling-eigenvalue metrics of INFERENCE.py: mean / min / max APE in percent."""
+             device=None, bf16: Optional[bool] = None) -> Dict[str, float]:
+    """Buckling-eigenvalue metrics of INFERENCE.py: mean / min / max APE in percent.
+    bf16: None leaves the model's `infer_bf16` flag alone; True / False sets it for this call (the
+    GraphSAGE sum / mean models' bf16 inference path, BuckGNN.infer_bf16) and restores it after."""
     model.eval()
+    if bf16 is None:
+        return _evaluate(model, batches, normalizer, device)
+    had = "infer_bf16" in vars(model)
+    before = getattr(model, "infer_bf16", False)
+    model.infer_bf16 = bool(bf16)
+    try:
+        return _evaluate(model, batches, normalizer, device)
+    finally:
+        if had:
+            model.infer_bf16 = before
+        else:
+            del model.infer_bf16
+
+
+def _evaluate(model, batches, normalizer, device) -> Dict[str, float]:
     total, n, lo, hi = 0.0, 0, float("inf"), 0.0
     preds = []
     for batch in batches:

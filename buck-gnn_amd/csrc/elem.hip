@@ -6,6 +6,7 @@
 //   bwd: g' = drop(g)         (dL/da = dL/db = g')
 // torch's add + dropout + masked-scale backward make 5.25 + 2.25 such passes.
 #include "common.h"
+#include "seg_common.h"
 
 namespace bgnn {
 
@@ -33,22 +34,7 @@ __global__ __launch_bounds__(256) void k_add_dropout(const float4* __restrict__ 
 
 // bf16 storage (the EA_GNN bf16 configuration's edge activations): 8 elements per thread, the
 // same mask (group index = element / 4), sums in f32, one round to nearest even per result
-__device__ __forceinline__ void bf16x8_unpack(const uint4 q, float (&f)[8]) {
-    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        f[2 * h] = __uint_as_float(w[h] << 16);
-        f[2 * h + 1] = __uint_as_float(w[h] & 0xffff0000u);
-    }
-}
-
-__device__ __forceinline__ uint32_t bf16_pack2(float x, float y) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const f32x2 v = {x, y};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
+// (bf16x8_unpack / bf16_pack2: seg_common.h)
 __global__ __launch_bounds__(256) void k_add_dropout_bf16(const uint4* __restrict__ a, const uint4* __restrict__ b,
                                                           int64_t n8, uint32_t thr, float inv_keep, uint64_t seed,
                                                           uint4* __restrict__ out) {

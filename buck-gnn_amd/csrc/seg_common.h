@@ -1,0 +1,68 @@
+// Helpers shared by the CSR aggregation kernels (spmm.hip, sage_infer.hip) and the bf16
+// element-wise kernels (elem.hip): the canonical SAGE row arithmetic, the XCD sweep's row
+// assignment, a lane's column positions and the bf16 pack / unpack of one 16-byte vector.
+#pragma once
+
+#include "common.h"
+
+namespace bgnn {
+
+// 1 / max(deg, 1), correctly rounded, identical in every kernel (MEAN backward weights)
+__device__ __forceinline__ float inv_deg(int32_t d) { return __frcp_rn((float)(d > 0 ? d : 1)); }
+
+// Canonical SAGE row arithmetic, written with explicit roundings so that every kernel
+// (light, sweep, combine) produces bit-identical o / nrm regardless of how the
+// compiler would contract it: h = (a * sc + zr) + b, ss = fma(h, h, ss).
+__device__ __forceinline__ float sage_h(float a, float sc, float zr, float b) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(a, sc), zr), b);
+}
+
+template <int VEC, int NV, int LPR>
+__device__ __forceinline__ void lane_cols(int cb, int lir, int H, int (&cpos)[NV], bool (&cok)[NV]) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        cpos[v] = cb + (lir + LPR * v) * VEC;
+        cok[v] = cpos[v] < H;
+    }
+}
+
+// Row (or row-group) assignment of the XCD sweep kernels: the grid (a multiple of 8 blocks) is
+// split into the 8 groups of blocks that share an XCD under round-robin dispatch (b % 8). Group x
+// owns the contiguous region [x*N/8, (x+1)*N/8) and its 4*G/8 waves sweep that region together:
+// wave q takes lo + q, lo + q + W, lo + q + 2W, ... (spmm.hip, "XCD sweep kernel").
+struct Sweep {
+    int64_t lo, hi, first;
+    int W, T;
+};
+
+__device__ __forceinline__ Sweep sweep_rows(int64_t n_rows, int wave) {
+    Sweep s;
+    const int G = gridDim.x;                 // multiple of 8
+    const int x = blockIdx.x & 7, i = blockIdx.x >> 3;
+    const int64_t lo = n_rows * x / kNumXcd, hi = n_rows * (x + 1) / kNumXcd;
+    s.W = 4 * (G >> 3);
+    s.lo = lo;
+    s.hi = hi;
+    s.first = lo + i * 4 + wave;
+    s.T = s.first < hi ? (int)((hi - s.first + s.W - 1) / s.W) : 0;
+    return s;
+}
+
+// bf16 storage: 8 elements per 16-byte vector, widened exactly / rounded to nearest even
+__device__ __forceinline__ void bf16x8_unpack(const uint4 q, float (&f)[8]) {
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        f[2 * h] = __uint_as_float(w[h] << 16);
+        f[2 * h + 1] = __uint_as_float(w[h] & 0xffff0000u);
+    }
+}
+
+__device__ __forceinline__ uint32_t bf16_pack2(float x, float y) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const f32x2 v = {x, y};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+
+}  // namespace bgnn

@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "gemm_common.h"
+#include "seg_common.h"
 
 namespace bgnn {
 
@@ -95,9 +96,7 @@ __device__ __forceinline__ void amax_flush_wave(uint32_t* amax, uint32_t m) {
     if ((threadIdx.x & 63) == 0 && m) atomicMax(amax, m);
 }
 
-
-// 1 / max(deg, 1), correctly rounded, identical in every kernel (MEAN backward weights)
-__device__ __forceinline__ float inv_deg(int32_t d) { return __frcp_rn((float)(d > 0 ? d : 1)); }
+// (inv_deg, sage_h, lane_cols, Sweep / sweep_rows: seg_common.h)
 
 template <int VEC>
 struct Vec {
@@ -327,14 +326,8 @@ __device__ __forceinline__ void store_plain(const SegArgs& A, Acc<VEC, NV, OP>& 
 }
 
 // Fused SAGE epilogue for one row held by a full wave (LPR == 64, VEC == 4):
-// h = acc*scale + z_r[r] + b; o = h / max(||h||, 1e-12); BN partial sums.
-// Canonical SAGE row arithmetic, written with explicit roundings so that every kernel
-// (light, sweep, combine) produces bit-identical o / nrm regardless of how the
-// compiler would contract it: h = (a * sc + zr) + b, ss = fma(h, h, ss).
-__device__ __forceinline__ float sage_h(float a, float sc, float zr, float b) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(a, sc), zr), b);
-}
-
+// h = acc*scale + z_r[r] + b; o = h / max(||h||, 1e-12); BN partial sums (the row arithmetic
+// is sage_h, seg_common.h).
 template <int NV, int OP>
 __device__ __forceinline__ void store_sage(const SegArgs& A, Acc<4, NV, OP>& acc, int64_t r,
                                            int32_t deg, const int (&cpos)[NV], const bool (&cok)[NV],
@@ -373,15 +366,6 @@ __device__ __forceinline__ void store_sage(const SegArgs& A, Acc<4, NV, OP>& acc
         st<4>(A.out + r * A.ldo + cpos[v], o);
     }
     if ((threadIdx.x & 63) == 0) A.nrm[r] = n;
-}
-
-template <int VEC, int NV, int LPR>
-__device__ __forceinline__ void lane_cols(int cb, int lir, int H, int (&cpos)[NV], bool (&cok)[NV]) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        cpos[v] = cb + (lir + LPR * v) * VEC;
-        cok[v] = cpos[v] < H;
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -610,24 +594,7 @@ __global__ __launch_bounds__(1024) void k_seg_combine(SegArgs A) {
 // holds row t0+l); a row's col indices are one vector load (lane k = k-th
 // neighbour, deg <= chunk <= 64) issued one row ahead; up to U neighbours are
 // gathered in a single batch, so a light row costs about one memory round trip.
-struct Sweep {
-    int64_t lo, hi, first;
-    int W, T;
-};
-
-__device__ __forceinline__ Sweep sweep_rows(int64_t n_rows, int wave) {
-    Sweep s;
-    const int G = gridDim.x;                 // multiple of 8
-    const int x = blockIdx.x & 7, i = blockIdx.x >> 3;
-    const int64_t lo = n_rows * x / kNumXcd, hi = n_rows * (x + 1) / kNumXcd;
-    s.W = 4 * (G >> 3);
-    s.lo = lo;
-    s.hi = hi;
-    s.first = lo + i * 4 + wave;
-    s.T = s.first < hi ? (int)((hi - s.first + s.W - 1) / s.W) : 0;
-    return s;
-}
-
+// (Sweep / sweep_rows: seg_common.h)
 template <int NV, int OP, int U>
 __device__ __forceinline__ void sweep_gather(const SegArgs& A, Acc<4, NV, OP>& acc, int32_t cur, int32_t beg,
                                              int32_t deg, int32_t e0, const int (&cpos)[NV], const bool (&cok)[NV]) {

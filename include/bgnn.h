@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 13
+#define BGNN_ABI_VERSION 14
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -309,6 +309,28 @@ int bgnn_sage_apply(const float* o, const float* scale, const float* shift,
 /* ranges (optional, the next layer's forward-CSR bgnn_heavy_ranges buffer): also the range
  * partials of x_next (bgnn_range_partial_bytes; finish with bgnn_range_sums_finish mode 0), by a
  * row-blocked form of the same element-wise pass (the same x_next bits). */
+
+/* Eval-mode SAGE layer on bf16 rows (ABI 14): the aggregation of bgnn_sage_fwd and the tail of
+ * bgnn_sage_apply (no dropout) in one pass over z = x [W_l ; W_r]^T stored as bf16 [N, 2H]
+ * (z_l = columns [0, H), z_r = columns [H, 2H); bgnn_gemm_bf16 storage 7). Per row i, in f32:
+ *   h = s_i * sum_{e in row i} z_l[col[e]] + z_r[i] + bias     (s_i = 1, or 1 / max(deg, 1) for MEAN;
+ *                                                              empty rows aggregate to 0)
+ *   o = h / max(||h||_2, 1e-12)
+ *   y = ReLU(o * scale + shift)    (scale / shift from bgnn_bn_eval_coeffs; both NULL: ReLU(o))
+ *   y += x_prev[i]                 (x_prev bf16 [N, H], NULL: no skip)
+ * and y is stored once: rounded to bf16 (nearest even) into out [N, H], or as f32 when out_f32 = 1
+ * (the last layer, whose consumers are f32). ld* in elements of the stored type.
+ * Light rows (deg <= csr->chunk) take the CSR's row-group plan (one 16-byte load per lane and
+ * source row); a CSR without one takes one row per wave. Heavy rows use the chunk plan: f32 chunk
+ * sums into `partial` (n_chunks * H floats), combined in chunk order. No atomics: deterministic.
+ * The CSR's `ranges` are not used. BGNN_E_ARG, before anything is launched, when: H % 8 != 0 or
+ * H > 512; reduce is not SUM / MEAN; csr, z or out is NULL; ldz / ldx / ldo is not a multiple of 8
+ * (4 for an f32 out) or too small; exactly one of scale / shift is NULL; the CSR has heavy rows
+ * and partial is NULL; a pointer is not 16-byte aligned. */
+int bgnn_sage_infer_bf16(const bgnn_csr_t* csr, const void* z, int64_t ldz, const float* bias,
+                         const float* scale, const float* shift, const void* x_prev, int64_t ldx,
+                         int32_t H, int32_t reduce, void* out, int64_t ldo, int32_t out_f32,
+                         float* partial, void* stream);
 
 /* Backward pass 1: BatchNorm statistics of the incoming gradient g (= dL/dx_next):
  *   g2 = relu'(o*scale+shift) * dropout'(g);  partial sums of g2 and g2*xhat.
