@@ -1,5 +1,6 @@
 """GPU: bgnn_gemm_f32 (f32 MFMA and f16x3 kernel families) against an fp64 torch
-reference, all transposes, ragged shapes, split-K, beta accumulation, operand scaling."""
+reference, all transposes, ragged shapes, split-K, beta accumulation, operand scaling.
+The small-shape reference matrix over every tile config and epilogue path is tests/test_gpu_gemm_matrix.py."""
 import pytest
 import torch
 
