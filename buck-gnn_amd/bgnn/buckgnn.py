@@ -252,7 +252,10 @@ class BuckGNN(nn.Module):
         return dec(h) if out is None else out
 
     def _fused_ok(self, x: Tensor) -> bool:
-        return self.use_fused and x.is_cuda and self.hidden_channels % 4 == 0 and self.hidden_channels <= 512
+        # float32 activations only: the fused kernels read f32 rows, so a bf16 activation (the
+        # torch encoder's output under autocast, a bf16 input) takes the per-module loop
+        return (self.use_fused and x.is_cuda and x.dtype == torch.float32 and self.hidden_channels % 4 == 0
+                and self.hidden_channels <= 512)
 
     def _sage_fused(self, x: Tensor, aggr: str) -> bool:
         return self._fused_ok(x) and aggr in ("add", "sum", "mean", "max")

@@ -547,12 +547,22 @@ def _mlp2_prefix(mods, x: torch.Tensor) -> bool:
     return bool(_lib.query("bgnn_mlp2_supported", l1.in_features, l1.out_features, l2.out_features))
 
 
+def _require_f32(x: torch.Tensor, what: str) -> None:
+    """The f32-accurate fused path reads float32 rows; its custom functions ignore autocast, so a
+    bf16 activation can only come from the caller (handing it to the kernels would read past the
+    end of its buffer)."""
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what}: the fused path takes float32 activations (got {x.dtype}); bf16 features run on "
+                        "the per-module path (bgnn.nn.SAGEConv)")
+
+
 def mlp(seq: torch.nn.Sequential, x: torch.Tensor, return_amax: bool = False, bf16: bool = False):
     """Run an nn.Sequential of Linear/ReLU through bgnn GEMMs, fusing each ReLU into the
     preceding Linear's epilogue (same parameters, same result as seq(x)); a leading
     Linear(16,64).ReLU.Linear(64,128).ReLU runs as one bgnn_mlp2 kernel. With return_amax,
     also returns max|output| (device scalar) when the last module is a Linear or that kernel's
     ReLU, else None."""
+    _require_f32(x, "mlp")
     mods = list(seq)
     i = 0
     amax = None
@@ -1261,6 +1271,7 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
     pool: a SegmentIndex (sum / mean only): also return the mean pool of x_next per segment as the
     last element (SageLayerFn)."""
     require_cuda(x_prev, w_l, b_l, w_r, what="sage_layer")
+    _require_f32(x_prev, "sage_layer")
     H = w_l.size(0)
     if w_in is None and x_prev.size(1) != H:
         raise ValueError(f"sage_layer: x has {x_prev.size(1)} features, the layer {H}")
@@ -1404,6 +1415,7 @@ def sage_conv(x: torch.Tensor, w_l: torch.Tensor, b_l, w_r: torch.Tensor, graph:
     """normalize(lin_l(AGG x) + lin_r(x)) of one SAGEConv module on the hand-written path
     (SageConvFn); reduce 0 = sum/add, 1 = mean, 2 = max (aggregate-first)."""
     require_cuda(x, w_l, w_r, what="sage_conv")
+    _require_f32(x, "sage_conv")
     return SageConvFn.apply(x, w_l, b_l, w_r, graph, reduce)
 
 

@@ -46,8 +46,22 @@ class Linear(nn.Linear):
                 self.bias.uniform_(-b, b)
 
 
+def _apply_linear(lin: nn.Linear, x: Tensor, bias: bool = True) -> Tensor:
+    """lin(x) (bias=False: without its bias). Outside autocast, parameters of another float dtype
+    than x (a bf16 input to a float32 module) are cast to x's dtype, as autocast would."""
+    w, b = lin.weight, lin.bias if bias else None
+    if w.dtype != x.dtype and x.is_floating_point() and not torch.is_autocast_enabled(x.device.type):
+        return F.linear(x, w.to(x.dtype), None if b is None else b.to(x.dtype))
+    return lin(x) if (bias or lin.bias is None) else F.linear(x, w)
+
+
 class SAGEConv(nn.Module):
-    """GraphSAGE operator with PyG's constructor, forward and state-dict layout."""
+    """GraphSAGE operator with PyG's constructor, forward and state-dict layout.
+
+    dtypes: float32 input outside autocast runs in float32. A bfloat16 input, or a float32 / bf16
+    input under torch.autocast("cuda", dtype=torch.bfloat16), runs in bf16 (_fast_bf16, else the
+    generic aggregate + Linear branch); the output is then the input's dtype outside autocast and,
+    under autocast, float32 with normalize=True (torch's F.normalize there) and bf16 without."""
 
     def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, aggr: str = "mean",
                  normalize: bool = False, root_weight: bool = True, project: bool = False, bias: bool = True,
@@ -88,7 +102,10 @@ class SAGEConv(nn.Module):
         if self.project:
             x_src = F.relu(self.lin(x_src))
         graph = graph_for(edge_index, x_src.size(0))
-        if self._fast(x_src, x_dst):
+        b16 = self._bf16_context(x_src)
+        if b16 and self._fast_bf16(x_src, x_dst):
+            return self._forward_bf16(x_src, graph)
+        if not b16 and self._fast(x_src, x_dst):
             # the hand-written path: f16x3 MFMA transform [W_l;W_r] + fused aggregation, bias and
             # L2 normalize, with its own backward (bgnn.fused.SageConvFn)
             from .fused import sage_conv
@@ -97,16 +114,57 @@ class SAGEConv(nn.Module):
         if self.aggr in ("add", "sum", "mean") and 2 * self.out_channels <= self.in_channels[0]:
             # narrow output (e.g. SAGPooling's 1-channel scorer): transform first, then aggregate
             # the narrow rows -- lin_l(AGG x) = AGG(x W_l^T) + b_l, since sum / mean are linear
-            out = aggregate(F.linear(x_src, self.lin_l.weight), graph, self.aggr)
+            out = aggregate(_apply_linear(self.lin_l, x_src, bias=False), graph, self.aggr)
             if self.lin_l.bias is not None:
-                out = out + self.lin_l.bias
+                out = out + self.lin_l.bias.to(out.dtype)
         else:
-            out = self.lin_l(aggregate(x_src, graph, self.aggr))
+            out = _apply_linear(self.lin_l, aggregate(x_src, graph, self.aggr))
         if self.root_weight and x_dst is not None:
-            out = out + self.lin_r(x_dst)
+            out = out + _apply_linear(self.lin_r, x_dst)
         if self.normalize:
             out = F.normalize(out, p=2.0, dim=-1)
         return out
+
+    @staticmethod
+    def _bf16_context(x: Tensor) -> bool:
+        """bf16 input, or bf16 autocast on CUDA over a float32 / bf16 input."""
+        if x.dtype == torch.bfloat16:
+            return True
+        return (x.is_cuda and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda")
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+    def _fast_bf16(self, x_src: Tensor, x_dst: Tensor) -> bool:
+        """Whether a call in a bf16 context runs transform-first on the bf16 kernels
+        (_forward_bf16): sum / mean aggregation, root weight, no projection, float32 parameters
+        and an output of whole 16-byte bf16 vectors up to 512 wide."""
+        return (FAST_SAGECONV and self.root_weight and not self.project
+                and self.aggr in ("add", "sum", "mean") and x_src is x_dst and x_src.is_cuda and x_src.dim() == 2
+                and self.out_channels % 8 == 0 and 8 <= self.out_channels <= 512
+                and self.in_channels[0] % 8 == 0
+                and self.lin_l.weight.dtype == torch.float32 and self.lin_r.weight.dtype == torch.float32)
+
+    def _forward_bf16(self, x: Tensor, graph) -> Tensor:
+        """z = x [W_l ; W_r]^T as bf16 [N, 2 out] from one MFMA product (fused.linear_bf16), then
+        h = AGG z_l + z_r + b_l in f32 (the bf16 aggregation reads z_l in place and keeps its f32
+        accumulator) and the optional L2 normalize in f32; each piece carries its own autograd."""
+        from .fused import infer_weights, linear_bf16
+        out = self.out_channels
+        if torch.is_grad_enabled():
+            wcat = torch.cat([self.lin_l.weight, self.lin_r.weight], 0)
+        else:
+            wcat = infer_weights(self)   # bf16 [2 out, in], built once per weight version
+            x = x.to(torch.bfloat16)     # (a bf16 weight goes with bf16 rows)
+        autocast = torch.is_autocast_enabled("cuda")
+        with torch.autocast("cuda", enabled=False):
+            z = linear_bf16(x, wcat)
+            h = aggregate(z[:, :out], graph, self.aggr, out_dtype=torch.float32) + z[:, out:]
+            if self.lin_l.bias is not None:
+                h = h + self.lin_l.bias
+            if self.normalize:
+                h = F.normalize(h, p=2.0, dim=-1)
+        if autocast:   # torch's own dtypes there: F.normalize returns f32, a Linear bf16
+            return h if self.normalize else h.to(torch.bfloat16)
+        return h.to(x.dtype)
 
     def _fast(self, x_src: Tensor, x_dst: Tensor) -> bool:
         """Whether this call runs on bgnn.fused.SageConvFn: normalize=True, sum/mean/max

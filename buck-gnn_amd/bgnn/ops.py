@@ -4,6 +4,9 @@
   (PyG semantics: sum over in-edges of target = edge_index[1]; 'add' == 'sum';
   mean divides by the in-degree; max takes the element-wise maximum; empty
   rows are 0 for all three). Used at Models/BuckGNN.py:342,393,434,449,463.
+  float32 or bfloat16 features: bf16 sum / mean rows of whole 16-byte vectors run on the bf16
+  kernels (csrc/spmm_b16.hip), forward and backward; every other bf16 case is upcast, run on the
+  float32 kernels and rounded once.
 * `segment_reduce(src, segments, reduce)` — global_mean_pool
   (Models/BuckGNN.py:274) and torch_scatter.scatter_add / scatter_mean
   (Models/BuckGNN.py:561,605).
@@ -18,10 +21,14 @@ from .graph import Graph, SegmentIndex, _stream, require_cuda
 REDUCE = {"sum": 0, "add": 0, "mean": 1, "max": 2}
 
 
-def _check_x(x: torch.Tensor, what: str) -> torch.Tensor:
+def _check_x(x: torch.Tensor, what: str, bf16: bool = False) -> torch.Tensor:
     require_cuda(x, what=what)
+    if x.dtype == torch.bfloat16 and bf16:
+        if x.dim() != 2:
+            raise ValueError(f"{what}: expected a 2-D [rows, channels] tensor, got {tuple(x.shape)}")
+        return x   # (a strided view may run as it is: _b16_rows)
     if x.dtype != torch.float32:
-        raise TypeError(f"{what}: only float32 features are supported (got {x.dtype})")
+        raise TypeError(f"{what}: only float32{' / bfloat16' if bf16 else ''} features are supported (got {x.dtype})")
     if x.dim() != 2:
         raise ValueError(f"{what}: expected a 2-D [rows, channels] tensor, got {tuple(x.shape)}")
     return x.contiguous()
@@ -91,6 +98,61 @@ def max_arg_positions(csr, arg: torch.Tensor, rows: int, H: int) -> torch.Tensor
     return torch.where(deg.view(-1, 1) > 0, pos, torch.full_like(pos, -1))
 
 
+def _b16_width(H: int) -> bool:
+    """Row widths of the bf16 aggregation kernels: whole 16-byte vectors, at most one per lane."""
+    return H % 8 == 0 and 8 <= H <= 512
+
+
+def _b16_rows(t: torch.Tensor) -> bool:
+    """Whether the bf16 kernels can read t where it lies: unit column stride, rows a multiple of
+    8 elements apart and a 16-byte aligned base (a column slice z[:, :H] of a wider tensor is)."""
+    return (t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= t.size(1) and t.data_ptr() % 16 == 0)
+
+
+def spmm_fwd_bf16(csr, x: torch.Tensor, reduce: int, out_rows: int, out_f32: bool = False) -> torch.Tensor:
+    """sum / mean over the CSR rows of bf16 source rows (bgnn_spmm_fwd_bf16): f32 accumulation, the
+    result stored once as bf16, or f32 with out_f32. x: bf16 [*, H] that satisfies _b16_rows."""
+    H = x.size(1)
+    out = torch.empty(out_rows, H, dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+    part = _partial(csr, H, 0, x.device)
+    if out_rows > 0:
+        _lib.call("bgnn_spmm_fwd_bf16", csr.ref(), x.data_ptr(), x.stride(0), H, reduce, out.data_ptr(),
+                  out.stride(0), int(out_f32), None if part is None else part.data_ptr(), _stream())
+    return out
+
+
+def spmm_bwd_bf16(csr_t, fwd_rowptr, g: torch.Tensor, reduce: int, out_rows: int, out_f32: bool = False):
+    """The transpose of spmm_fwd_bf16 over bf16 gradient rows (bgnn_spmm_bwd_bf16; rows = sources)."""
+    H = g.size(1)
+    gx = torch.empty(out_rows, H, dtype=torch.float32 if out_f32 else torch.bfloat16, device=g.device)
+    part = _partial(csr_t, H, 0, g.device)
+    if out_rows > 0:
+        _lib.call("bgnn_spmm_bwd_bf16", csr_t.ref(), None if fwd_rowptr is None else fwd_rowptr.data_ptr(),
+                  g.data_ptr(), g.stride(0), H, reduce, gx.data_ptr(), gx.stride(0), int(out_f32),
+                  None if part is None else part.data_ptr(), _stream())
+    return gx
+
+
+class _AggregateBf16(torch.autograd.Function):
+    """sum / mean aggregation of bf16 rows on the bf16 kernels, output bf16 or f32; the backward
+    gathers the incoming gradient as bf16 (a f32 gradient is rounded once) and returns bf16."""
+
+    @staticmethod
+    def forward(ctx, x, graph: Graph, reduce: int, out_f32: bool):
+        ctx.graph = graph
+        ctx.reduce = reduce
+        return spmm_fwd_bf16(graph.fwd, x, reduce, graph.num_nodes, out_f32)
+
+    @staticmethod
+    def backward(ctx, g):
+        graph = ctx.graph
+        if g.dtype != torch.bfloat16:
+            g = g.to(torch.bfloat16)
+        if not _b16_rows(g):
+            g = g.contiguous()
+        return spmm_bwd_bf16(graph.bwd, graph.fwd.rowptr, g, ctx.reduce, graph.num_nodes), None, None, None
+
+
 class _Aggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, graph: Graph, reduce: int):
@@ -109,13 +171,27 @@ class _Aggregate(torch.autograd.Function):
         return gx, None, None
 
 
-def aggregate(x: torch.Tensor, graph: Graph, reduce: str = "sum") -> torch.Tensor:
-    """out[i] = AGG_{j: (j -> i) in E} x[j]  (PyG SAGEConv aggregation)."""
-    x = _check_x(x, "aggregate")
+def aggregate(x: torch.Tensor, graph: Graph, reduce: str = "sum", out_dtype=None) -> torch.Tensor:
+    """out[i] = AGG_{j: (j -> i) in E} x[j]  (PyG SAGEConv aggregation), in x's dtype.
+    bfloat16 x: out_dtype=torch.float32 keeps the f32 accumulator's value instead of rounding it to
+    bf16. sum / mean over rows the bf16 kernels can read in place (_b16_width, _b16_rows: a column
+    slice of a wider tensor included) run on them, forward and backward; every other case -- max,
+    other widths or layouts -- is upcast, run on the float32 kernels and rounded once (exact for
+    max: the maximum of bf16 values is one of them; ties and the argmax backward are those
+    kernels' own)."""
+    x = _check_x(x, "aggregate", bf16=True)
     if x.size(0) != graph.num_nodes:
         raise ValueError(f"aggregate: x has {x.size(0)} rows, graph has {graph.num_nodes} nodes")
+    if out_dtype not in (None, x.dtype, torch.float32):
+        raise TypeError(f"aggregate: out_dtype must be the input's dtype or float32 (got {out_dtype})")
     r = REDUCE[reduce]
-    return _Aggregate.apply(x, graph, r)
+    if x.dtype == torch.float32:
+        return _Aggregate.apply(x, graph, r)
+    out_f32 = out_dtype == torch.float32
+    if r != 2 and _b16_width(x.size(1)) and _b16_rows(x):
+        return _AggregateBf16.apply(x, graph, r, out_f32)
+    out = _Aggregate.apply(x.float().contiguous(), graph, r)
+    return out if out_f32 else out.to(torch.bfloat16)
 
 
 class _SegmentReduce(torch.autograd.Function):
@@ -182,6 +258,9 @@ def segment_reduce(src: torch.Tensor, seg: SegmentIndex, reduce: str = "sum") ->
         if src.dim() != 2 or src.size(0) != seg.n or src.size(1) % 8 or src.size(1) > 512:
             raise ValueError("segment_reduce(bf16): need [n, H] with H % 8 == 0, H <= 512")
         return _SegmentReduceBf16.apply(src, seg, reduce == "mean")
+    if src.dtype == torch.bfloat16 and reduce == "max":
+        # exact through the float32 kernel: the maximum of bf16 values is one of them
+        return segment_reduce(src.float(), seg, reduce).to(torch.bfloat16)
     src = _check_x(src, "segment_reduce")
     if src.size(0) != seg.n:
         raise ValueError(f"segment_reduce: src has {src.size(0)} rows, index has {seg.n} entries")

@@ -1,4 +1,4 @@
-// Helpers shared by the CSR aggregation kernels (spmm.hip, sage_infer.hip) and the bf16
+// Helpers shared by the CSR aggregation kernels (spmm.hip, sage_infer.hip, spmm_b16.hip) and the bf16
 // element-wise kernels (elem.hip): the canonical SAGE row arithmetic, the XCD sweep's row
 // assignment, a lane's column positions and the bf16 pack / unpack of one 16-byte vector.
 #pragma once

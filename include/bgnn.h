@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 14
+#define BGNN_ABI_VERSION 15
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -331,6 +331,32 @@ int bgnn_sage_infer_bf16(const bgnn_csr_t* csr, const void* z, int64_t ldz, cons
                          const float* scale, const float* shift, const void* x_prev, int64_t ldx,
                          int32_t H, int32_t reduce, void* out, int64_t ldo, int32_t out_f32,
                          float* partial, void* stream);
+
+/* Neighbour aggregation of bf16 rows and its transpose (ABI 15): bgnn_spmm_fwd / bgnn_spmm_bwd for
+ * SUM and MEAN over bf16 storage -- the aggregation of the PyG surface (bgnn.ops.aggregate,
+ * bgnn.nn.SAGEConv) on bf16 features, e.g. under torch.autocast. Per row, in f32:
+ *   forward : out[r, :] = s_r * sum_{e in row r} x[col[e], :]
+ *             s_r = 1 (SUM), 1 / max(deg r, 1) (MEAN); empty rows give 0
+ *   backward: gx[j, :]  = sum_{q in rowT j} w(t_q) * g[t_q, :],  t_q = col_t[q]  (csr_t = the
+ *             transpose CSR, rows = sources); w(t) = 1 (SUM), 1 / max(deg_fwd(t), 1) (MEAN), with
+ *             deg_fwd from fwd_rowptr, the forward CSR's rowptr
+ * x / g: bf16 [*, ld]; f32 accumulation; the result is stored once: rounded to bf16 (nearest even),
+ * or as f32 when out_f32 = 1. ld* in elements of the stored type. A source row is one 16-byte load
+ * per lane (8 lines of 128 B at H = 512, the f32 kernels read 16). Light rows (deg <= csr->chunk)
+ * take the CSR's row-group plan (group_rows 4 or 8, chunk <= 64); a CSR without one takes one row
+ * per wave. Heavy rows use the chunk plan: f32 chunk sums into `partial` (n_chunks * H floats),
+ * combined in chunk order. No atomics: every row's summation order is fixed by the plan, so the
+ * result is bit-identical run to run. The CSR's `ranges` are not used. BGNN_E_ARG, before anything
+ * is launched, when: H % 8 != 0 or H > 512; reduce is not SUM / MEAN (MAX: upcast and use
+ * bgnn_spmm_fwd); csr, x / g or out / gx is NULL; ldx / ldg is < H or not a multiple of 8; ldo /
+ * ldgx is < H or not a multiple of 8 (4 for an f32 output); a pointer is not 16-byte aligned; the
+ * CSR has chunks and partial is NULL or the chunk plan is incomplete; MEAN backward without
+ * fwd_rowptr. n_rows <= 0 returns BGNN_OK without a launch. */
+int bgnn_spmm_fwd_bf16(const bgnn_csr_t* csr, const void* x, int64_t ldx, int32_t H, int32_t reduce,
+                       void* out, int64_t ldo, int32_t out_f32, float* partial, void* stream);
+int bgnn_spmm_bwd_bf16(const bgnn_csr_t* csr_t, const int32_t* fwd_rowptr, const void* g, int64_t ldg,
+                       int32_t H, int32_t reduce, void* gx, int64_t ldgx, int32_t out_f32,
+                       float* partial, void* stream);
 
 /* Backward pass 1: BatchNorm statistics of the incoming gradient g (= dL/dx_next):
  *   g2 = relu'(o*scale+shift) * dropout'(g);  partial sums of g2 and g2*xhat.
