@@ -203,6 +203,8 @@ class BuckGNN(nn.Module):
         # GraphSAGE sum / mean models, eval mode under no_grad on the fused path: bf16 layer rows and
         # one bf16 MFMA product per GEMM, each layer a GEMM plus one aggregation + tail kernel
         # (fused.sage_infer_layer). Off: the f32-accurate path, as in training. (_infer_bf16_on)
+        # "all": as True, and GraphSage_maxAggr too, on bf16 rows with a gather, a K = 2H GEMM and a
+        # tail kernel per layer (fused.sage_infer_max_layer); under True a max model stays f32.
         self.infer_bf16 = False
         self._step = 0
 
@@ -262,11 +264,14 @@ class BuckGNN(nn.Module):
 
     def _infer_bf16_on(self, x: Tensor, aggr: str, bns) -> bool:
         """Whether the SAGE layer loop takes the bf16 inference path (infer_bf16): eval mode without
-        autograd on the fused path, a sum / mean aggregation, rows of whole 16-byte bf16 vectors
-        and BatchNorms with running statistics (their scale / shift are then known up front)."""
+        autograd on the fused path, a sum / mean aggregation (max too when the flag is "all"), rows
+        of whole 16-byte bf16 vectors and BatchNorms with running statistics (their scale / shift
+        are then known up front)."""
         h = self.hidden_channels
+        # (max only under infer_bf16 == "all": True keeps the meaning it had before the max path)
+        aggrs = ("add", "sum", "mean", "max") if self.infer_bf16 == "all" else ("add", "sum", "mean")
         return bool(self.infer_bf16 and not self.training and not torch.is_grad_enabled()
-                    and self._fused_ok(x) and aggr in ("add", "sum", "mean") and h % 8 == 0 and h <= 512
+                    and self._fused_ok(x) and aggr in aggrs and h % 8 == 0 and h <= 512
                     and (bns is None or all(bn.track_running_stats and bn.running_mean is not None
                                             for bn in bns)))
 
@@ -275,6 +280,9 @@ class BuckGNN(nn.Module):
         tail kernel; the last layer writes f32 for the pooling and the decoder."""
         L = len(convs) if convs is not None else self.num_layers
         graph = graph_for(edge_index, x.size(0))
+        if aggr == "max":
+            x = self._sage_loop_bf16_max(x, graph, convs, bns, L)
+            return (x, segment_reduce(x, pool, "mean")) if pool is not None else x
         red = 1 if aggr == "mean" else 0
         for i in range(L):
             conv = convs[i] if convs is not None else self.shared_graphsage_block
@@ -282,6 +290,30 @@ class BuckGNN(nn.Module):
             x = _fused.sage_infer_layer(x, _fused.infer_weights(conv), conv.lin_l.bias, coeffs, graph, red,
                                         x_prev=x if 0 < i < L - 1 else None, out_f32=i == L - 1)
         return (x, segment_reduce(x, pool, "mean")) if pool is not None else x
+
+    def _sage_loop_bf16_max(self, x: Tensor, graph, convs, bns, L: int) -> Tensor:
+        """The eval-mode max-aggregation layer loop on bf16 rows (infer_bf16 = "all"): max is not
+        linear, so each layer aggregates first and transforms [agg | x] in one GEMM
+        (fused.sage_infer_max_layer: gather, GEMM, tail). Two ping-pong [N, 2H] bf16 buffers hold
+        [agg | x]: a layer's tail writes plane 1 of the other buffer, where the next layer's gather
+        reads it; the last layer writes f32 for the pooling and the decoder."""
+        if L == 0:
+            return x
+        N, H = x.size(0), self.hidden_channels
+        bufs = [torch.empty(N, 2 * H, dtype=torch.bfloat16, device=x.device) for _ in range(min(L, 2))]
+        y = torch.empty(N, H, dtype=torch.bfloat16, device=x.device)
+        bufs[0][:, H:].copy_(x)   # the encoder's f32 output, rounded to bf16 once
+        out = None
+        for i in range(L):
+            conv = convs[i] if convs is not None else self.shared_graphsage_block
+            coeffs = _fused.bn_eval_coeffs(bns[i]) if bns is not None else None
+            cur = bufs[i % 2]
+            last = i == L - 1
+            out = (torch.empty(N, H, dtype=torch.float32, device=x.device) if last
+                   else bufs[(i + 1) % 2][:, H:])
+            _fused.sage_infer_max_layer(cur, _fused.infer_weights_max(conv), conv.lin_l.bias, coeffs, graph,
+                                        cur[:, H:] if 0 < i < L - 1 else None, out, out_f32=last, y=y)
+        return out
 
     def _foldable_encoder(self, x: Tensor) -> bool:
         """The node encoder's last Linear can be folded into the first fused SAGE layer (which

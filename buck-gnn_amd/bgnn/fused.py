@@ -1487,3 +1487,64 @@ def sage_infer_layer(x: torch.Tensor, w_cat: torch.Tensor, bias, bn_coeffs, grap
                   _ptr(shift), _ptr(xp), xp.stride(0) if xp is not None else 0, H, reduce, out.data_ptr(),
                   out.stride(0), int(out_f32), _ptr(part), _stream())
     return out
+
+
+# ---------------------------------------------------------------------------
+# bf16 max-aggregation inference layer (BuckGNN.infer_bf16 = "all"): max is not linear, so the layer
+# aggregates first and transforms [agg | x] in one GEMM of K = 2H.
+
+def infer_weights_max(conv) -> torch.Tensor:
+    """[W_l | W_r] of a SAGEConv as one bf16 [H, 2H] matrix (the B^T operand of the max layer's
+    GEMM over [agg | x]), cached per weight version on the module as infer_weights is, under an
+    attribute of its own."""
+    w_l, w_r = conv.lin_l.weight, conv.lin_r.weight
+    key = (w_l._version, w_r._version, w_l.data_ptr(), w_r.data_ptr(), str(w_l.device))
+    hit = getattr(conv, "_bgnn_infer_wcat_max", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        wcat = torch.cat([w_l.detach(), w_r.detach()], 1).to(torch.bfloat16).contiguous()
+    conv._bgnn_infer_wcat_max = (key, wcat)
+    return wcat
+
+
+@torch.no_grad()
+def sage_infer_max_layer(buf: torch.Tensor, w: torch.Tensor, bias, bn_coeffs, graph: Graph, x_prev_plane,
+                         out: torch.Tensor, out_f32: bool = False, y: torch.Tensor = None) -> torch.Tensor:
+    """One eval-mode max-aggregation GraphSAGE layer on bf16 rows, three launches:
+        agg = max_{j->i} x[j]                     into plane 0 of buf = [agg | x]   bgnn_spmm_max_bf16
+        y   = buf [W_l | W_r]^T                   bf16 in, bf16 out, K = 2H          (gemm_bf16)
+        out = ReLU(BN(normalize(y + b))) (+ x_prev)                                 bgnn_sage_tail_bf16
+    buf: bf16 [N, 2H] whose plane 1 (columns [H, 2H)) holds the layer input x; w: bf16 [H, 2H]
+    (infer_weights_max); bias: f32 [H] or None; bn_coeffs: (scale, shift) f32 [H] or None;
+    x_prev_plane: the skip input, a bf16 [N, H] view (plane 1 of buf), or None; out: where the
+    result goes -- plane 1 of the next layer's buffer (bf16), or a contiguous f32 [N, H] with
+    out_f32 (the last layer); y: a bf16 [N, H] scratch to reuse across layers (None: a new one).
+    Returns out. No autograd."""
+    from .ops import spmm_max_bf16
+
+    require_cuda(buf, w, bias, x_prev_plane, out, what="sage_infer_max_layer")
+    N, H = buf.size(0), w.size(0)
+    if (buf.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or buf.dim() != 2 or buf.size(1) != 2 * H
+            or w.size(1) != 2 * H or not buf.is_contiguous()):
+        raise ValueError("sage_infer_max_layer: buf must be a contiguous bfloat16 [N, 2H] and w bfloat16 [H, 2H]")
+    if H % 8 or H > 512:
+        raise ValueError(f"sage_infer_max_layer: needs H % 8 == 0 and H <= 512 (got {H})")
+    if out.dtype != (torch.float32 if out_f32 else torch.bfloat16) or tuple(out.shape) != (N, H) or out.stride(1) != 1:
+        raise ValueError("sage_infer_max_layer: out must be [N, H] with unit column stride, f32 with out_f32 "
+                         "and bfloat16 without")
+    if x_prev_plane is not None and (x_prev_plane.dtype != torch.bfloat16 or tuple(x_prev_plane.shape) != (N, H)
+                                     or x_prev_plane.stride(1) != 1):
+        raise ValueError("sage_infer_max_layer: x_prev_plane must be a bfloat16 [N, H] view")
+    if y is None:
+        y = torch.empty(N, H, dtype=torch.bfloat16, device=buf.device)
+    with _timed("infer_max_agg"):
+        spmm_max_bf16(graph.fwd, buf[:, H:], N, False, out=buf[:, :H])
+    with _timed("infer_max_gemm"):
+        gemm_bf16(buf, w, trans_a=False, trans_b=True, out=y)
+    scale, shift = bn_coeffs if bn_coeffs is not None else (None, None)
+    with _timed("infer_max_tail"):
+        _lib.call("bgnn_sage_tail_bf16", y.data_ptr(), y.stride(0), _ptr(bias), _ptr(scale), _ptr(shift),
+                  _ptr(x_prev_plane), x_prev_plane.stride(0) if x_prev_plane is not None else 0, N, H,
+                  out.data_ptr(), out.stride(0), int(out_f32), _stream())
+    return out

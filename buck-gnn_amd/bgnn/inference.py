@@ -19,16 +19,17 @@ from .train import EigenvalueScaler
 
 @torch.no_grad()
 def evaluate(model, batches: Iterable, normalizer: Optional[EigenvalueScaler] = None,
-             device=None, bf16: Optional[bool] = None) -> Dict[str, float]:
+             device=None, bf16=None) -> Dict[str, float]:
     """Buckling-eigenvalue metrics of INFERENCE.py: mean / min / max APE in percent.
     bf16: None leaves the model's `infer_bf16` flag alone; True / False sets it for this call (the
-    GraphSAGE sum / mean models' bf16 inference path, BuckGNN.infer_bf16) and restores it after."""
+    GraphSAGE sum / mean models' bf16 inference path, BuckGNN.infer_bf16) and restores it after;
+    "all" is passed through as it is (the max-aggregation model's bf16 path too)."""
     model.eval()
     if bf16 is None:
         return _evaluate(model, batches, normalizer, device)
     had = "infer_bf16" in vars(model)
     before = getattr(model, "infer_bf16", False)
-    model.infer_bf16 = bool(bf16)
+    model.infer_bf16 = "all" if isinstance(bf16, str) and bf16 == "all" else bool(bf16)
     try:
         return _evaluate(model, batches, normalizer, device)
     finally:

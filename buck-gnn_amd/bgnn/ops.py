@@ -5,8 +5,9 @@
   mean divides by the in-degree; max takes the element-wise maximum; empty
   rows are 0 for all three). Used at Models/BuckGNN.py:342,393,434,449,463.
   float32 or bfloat16 features: bf16 sum / mean rows of whole 16-byte vectors run on the bf16
-  kernels (csrc/spmm_b16.hip), forward and backward; every other bf16 case is upcast, run on the
-  float32 kernels and rounded once.
+  kernels (csrc/spmm_b16.hip), forward and backward, and bf16 max rows on the bf16 max kernel
+  (csrc/spmm_max_b16.hip; its backward is the float32 argmax kernel); every other bf16 case is
+  upcast, run on the float32 kernels and rounded once.
 * `segment_reduce(src, segments, reduce)` — global_mean_pool
   (Models/BuckGNN.py:274) and torch_scatter.scatter_add / scatter_mean
   (Models/BuckGNN.py:561,605).
@@ -133,6 +134,46 @@ def spmm_bwd_bf16(csr_t, fwd_rowptr, g: torch.Tensor, reduce: int, out_rows: int
     return gx
 
 
+def spmm_max_bf16(csr, x: torch.Tensor, out_rows: int, want_arg: bool = False, out: torch.Tensor = None):
+    """max over the CSR rows of bf16 source rows (bgnn_spmm_max_bf16): exact, the values and ties of
+    spmm_fwd(MAX) on the upcast x. x: bf16 [*, H] that satisfies _b16_rows; out: a bf16 [out_rows, H]
+    destination that does too (a column plane of a wider buffer), or None for a new one. Returns
+    (out, arg): with want_arg the argmax state spmm_fwd(MAX) would have written (spmm_bwd reads it,
+    max_arg_positions decodes it)."""
+    H = x.size(1)
+    if out is None:
+        out = torch.empty(out_rows, H, dtype=torch.bfloat16, device=x.device)
+    arg = None
+    if want_arg:
+        arg = torch.empty(_lib.query("bgnn_spmm_max_arg_bytes", out_rows, H, csr.plan.n_heavy), dtype=torch.uint8,
+                          device=x.device)
+    part = _partial(csr, H, 2 if want_arg else 0, x.device)
+    if out_rows > 0:
+        _lib.call("bgnn_spmm_max_bf16", csr.ref(), x.data_ptr(), x.stride(0), H, out.data_ptr(), out.stride(0),
+                  None if arg is None else arg.data_ptr(), None if part is None else part.data_ptr(), _stream())
+    return out, arg
+
+
+class _AggregateMaxBf16(torch.autograd.Function):
+    """max aggregation of bf16 rows on the bf16 kernel, output bf16 or its exact f32 widening. The
+    backward is the f32 route's: the gradient upcast to f32, bgnn_spmm_bwd_max on the saved argmax
+    state, the result rounded to bf16 once."""
+
+    @staticmethod
+    def forward(ctx, x, graph: Graph, out_f32: bool):
+        out, arg = spmm_max_bf16(graph.fwd, x, graph.num_nodes, want_arg=x.requires_grad)
+        ctx.graph = graph
+        ctx.save_for_backward(arg if arg is not None else torch.empty(0, device=x.device))
+        return out.float() if out_f32 else out
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        graph = ctx.graph
+        gx = spmm_bwd(graph.bwd, graph.perm_t, graph.fwd.rowptr, g.float(), 2, arg, graph.num_nodes)
+        return gx.to(torch.bfloat16), None, None
+
+
 class _AggregateBf16(torch.autograd.Function):
     """sum / mean aggregation of bf16 rows on the bf16 kernels, output bf16 or f32; the backward
     gathers the incoming gradient as bf16 (a f32 gradient is rounded once) and returns bf16."""
@@ -175,10 +216,11 @@ def aggregate(x: torch.Tensor, graph: Graph, reduce: str = "sum", out_dtype=None
     """out[i] = AGG_{j: (j -> i) in E} x[j]  (PyG SAGEConv aggregation), in x's dtype.
     bfloat16 x: out_dtype=torch.float32 keeps the f32 accumulator's value instead of rounding it to
     bf16. sum / mean over rows the bf16 kernels can read in place (_b16_width, _b16_rows: a column
-    slice of a wider tensor included) run on them, forward and backward; every other case -- max,
-    other widths or layouts -- is upcast, run on the float32 kernels and rounded once (exact for
-    max: the maximum of bf16 values is one of them; ties and the argmax backward are those
-    kernels' own)."""
+    slice of a wider tensor included) run on them, forward and backward; max over such rows runs
+    its forward on the bf16 max kernel (exact: the maximum of bf16 values is one of them; values,
+    ties and the argmax state are the float32 kernel's) and its backward on the float32 argmax
+    kernel, rounded once. Every other case -- other widths or layouts -- is upcast, run on the
+    float32 kernels and rounded once."""
     x = _check_x(x, "aggregate", bf16=True)
     if x.size(0) != graph.num_nodes:
         raise ValueError(f"aggregate: x has {x.size(0)} rows, graph has {graph.num_nodes} nodes")
@@ -188,7 +230,9 @@ def aggregate(x: torch.Tensor, graph: Graph, reduce: str = "sum", out_dtype=None
     if x.dtype == torch.float32:
         return _Aggregate.apply(x, graph, r)
     out_f32 = out_dtype == torch.float32
-    if r != 2 and _b16_width(x.size(1)) and _b16_rows(x):
+    if _b16_width(x.size(1)) and _b16_rows(x):
+        if r == 2:
+            return _AggregateMaxBf16.apply(x, graph, out_f32)
         return _AggregateBf16.apply(x, graph, r, out_f32)
     out = _Aggregate.apply(x.float().contiguous(), graph, r)
     return out if out_f32 else out.to(torch.bfloat16)

@@ -1,6 +1,7 @@
-// Helpers shared by the CSR aggregation kernels (spmm.hip, sage_infer.hip, spmm_b16.hip) and the bf16
-// element-wise kernels (elem.hip): the canonical SAGE row arithmetic, the XCD sweep's row
-// assignment, a lane's column positions and the bf16 pack / unpack of one 16-byte vector.
+// Helpers shared by the CSR aggregation kernels (spmm.hip, sage_infer.hip, spmm_b16.hip,
+// spmm_max_b16.hip) and the bf16 element-wise kernels (elem.hip): the canonical SAGE row arithmetic,
+// the XCD sweep's row assignment, a lane's column positions, the MAX argmax state's layout and the
+// bf16 pack / unpack of one 16-byte vector.
 #pragma once
 
 #include "common.h"
@@ -46,6 +47,21 @@ __device__ __forceinline__ Sweep sweep_rows(int64_t n_rows, int wave) {
     s.first = lo + i * 4 + wave;
     s.T = s.first < hi ? (int)((hi - s.first + s.W - 1) / s.W) : 0;
     return s;
+}
+
+// The MAX argmax state (bgnn_spmm_max_arg_bytes), written by bgnn_spmm_fwd(MAX) and
+// bgnn_spmm_max_bf16 and read by bgnn_spmm_bwd_max: a uint8 [rows, H] plane of edge offsets (heavy
+// rows hold kArgHeavy), then heavy_of int32 [rows], then arg_h int32 [n_heavy, H], each 256-byte
+// aligned.
+constexpr uint8_t kArgHeavy = 255;
+struct MaxArgLayout {
+    int64_t heavy_of, arg_h;
+};
+inline MaxArgLayout max_arg_layout(int64_t rows, int64_t H) {
+    MaxArgLayout L;
+    L.heavy_of = (int64_t)align_up((size_t)(rows * H), 256);
+    L.arg_h = L.heavy_of + (int64_t)align_up((size_t)(rows * 4), 256);
+    return L;
 }
 
 // bf16 storage: 8 elements per 16-byte vector, widened exactly / rounded to nearest even

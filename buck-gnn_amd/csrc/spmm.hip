@@ -175,8 +175,6 @@ struct Acc {
     }
 };
 
-constexpr uint8_t kArgHeavy = 255;
-
 // MAXT: the forward argmax bytes of (i, c..c+VEC-1), packed (VEC 4: one dword, VEC 1: one byte).
 // Loaded in the same batch as the x rows, so that a gather batch issues all its loads at once.
 template <int VEC>
@@ -1163,17 +1161,6 @@ int dispatch_plain(SegArgs A, const Geometry& g, hipStream_t s) {
     return fail(BGNN_E_UNSUPPORTED, "spmm: no kernel for vec=%d nv=%d lpr=%d", g.vec, g.nv, g.lpr);
 }
 
-
-// byte layout of the MAX argmax state buffer (bgnn_spmm_max_arg_bytes)
-struct MaxArgLayout {
-    int64_t heavy_of, arg_h;
-};
-inline MaxArgLayout max_arg_layout(int64_t rows, int64_t H) {
-    MaxArgLayout L;
-    L.heavy_of = (int64_t)align_up((size_t)(rows * H), 256);
-    L.arg_h = L.heavy_of + (int64_t)align_up((size_t)(rows * 4), 256);
-    return L;
-}
 
 inline SegArgs args_from_csr(const bgnn_csr_t* c) {
     SegArgs A{};

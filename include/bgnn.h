@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 15
+#define BGNN_ABI_VERSION 16
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -347,8 +347,8 @@ int bgnn_sage_infer_bf16(const bgnn_csr_t* csr, const void* z, int64_t ldz, cons
  * per wave. Heavy rows use the chunk plan: f32 chunk sums into `partial` (n_chunks * H floats),
  * combined in chunk order. No atomics: every row's summation order is fixed by the plan, so the
  * result is bit-identical run to run. The CSR's `ranges` are not used. BGNN_E_ARG, before anything
- * is launched, when: H % 8 != 0 or H > 512; reduce is not SUM / MEAN (MAX: upcast and use
- * bgnn_spmm_fwd); csr, x / g or out / gx is NULL; ldx / ldg is < H or not a multiple of 8; ldo /
+ * is launched, when: H % 8 != 0 or H > 512; reduce is not SUM / MEAN (MAX has a kernel of its own,
+ * bgnn_spmm_max_bf16 below); csr, x / g or out / gx is NULL; ldx / ldg is < H or not a multiple of 8; ldo /
  * ldgx is < H or not a multiple of 8 (4 for an f32 output); a pointer is not 16-byte aligned; the
  * CSR has chunks and partial is NULL or the chunk plan is incomplete; MEAN backward without
  * fwd_rowptr. n_rows <= 0 returns BGNN_OK without a launch. */
@@ -357,6 +357,48 @@ int bgnn_spmm_fwd_bf16(const bgnn_csr_t* csr, const void* x, int64_t ldx, int32_
 int bgnn_spmm_bwd_bf16(const bgnn_csr_t* csr_t, const int32_t* fwd_rowptr, const void* g, int64_t ldg,
                        int32_t H, int32_t reduce, void* gx, int64_t ldgx, int32_t out_f32,
                        float* partial, void* stream);
+
+/* Max aggregation of bf16 rows (ABI 16): bgnn_spmm_fwd(MAX) over bf16 storage,
+ *   out[r, :] = max_{e in row r} x[col[e], :]
+ * x: bf16 [*, ldx]; out: bf16 [n_rows, ldo]; ld* in elements. The semantics are exactly those of
+ * bgnn_spmm_fwd(MAX) on the upcast input: the accumulator starts at -inf, an edge replaces it only
+ * when strictly greater (the first maximising edge in CSR order wins, a NaN never wins), empty rows
+ * give 0. The maximum of bf16 values is one of them, so nothing is rounded: the result equals the
+ * f32 kernel's, value for value. A source row is one 16-byte load per lane (8 lines of 128 B at
+ * H = 512, the f32 kernel reads 16). x and out may be column planes of one wider allocation
+ * (ldx = ldo = 2H: out = plane 0, x = plane 1 of a [N, 2H] buffer).
+ * arg == NULL (inference): light rows (deg <= csr->chunk) take the CSR's row-group plan (group_rows
+ * 4 or 8, chunk <= 64; the plan lists a row's keys in edge order); a CSR without one takes one row
+ * per wave. arg != NULL: the argmax state of bgnn_spmm_max_arg_bytes(n_rows, H, n_heavy), in the
+ * layout bgnn_spmm_fwd writes and bgnn_spmm_bwd_max reads; light rows then run one row per wave
+ * and csr->chunk must be in [1, 254]. Heavy rows use the chunk plan: one wave per chunk writes
+ * `partial` (n_chunks * H floats; with arg a second plane of n_chunks * H int32 behind it), one
+ * wave per heavy row combines its chunks in chunk order. No atomics: bit-identical run to run. The
+ * CSR's `ranges` are not used. BGNN_E_ARG, before anything is launched, when: csr, x or out is
+ * NULL; H % 8 != 0, H < 8 or H > 512; ldx / ldo is < H or not a multiple of 8; x, out, arg or
+ * partial is not 16-byte aligned; the CSR has chunks and partial is NULL or the chunk plan is
+ * incomplete; arg with a chunk outside [1, 254]. n_rows <= 0 returns BGNN_OK without a launch. */
+int bgnn_spmm_max_bf16(const bgnn_csr_t* csr, const void* x, int64_t ldx, int32_t H,
+                       void* out, int64_t ldo, void* arg, float* partial, void* stream);
+
+/* The dense row tail of an eval-mode SAGE layer on bf16 rows (ABI 16): the tail of
+ * bgnn_sage_infer_bf16 with a zero aggregate, for a layer whose y = [agg | x] [W_l | W_r]^T is
+ * already complete (the max-aggregation inference layer, bgnn/fused.py sage_infer_max_layer).
+ * Per row i, in f32:
+ *   h = y[i] + bias                (y bf16 [n_rows, ldy]; bias NULL: 0)
+ *   o = h / max(||h||_2, 1e-12)
+ *   v = ReLU(o * scale + shift)    (scale / shift from bgnn_bn_eval_coeffs; both NULL: ReLU(o))
+ *   v += x_prev[i]                 (x_prev bf16 [n_rows, ldx], NULL: no skip)
+ * and v is stored once: rounded to bf16 (nearest even) into out [n_rows, ldo], or as f32 when
+ * out_f32 = 1. ld* in elements of the stored type; y, x_prev and out may be column planes of wider
+ * allocations. One wave per row; y and x_prev are read and out is written non-temporally. Both
+ * entry points compile one tail function, so a row with a zero aggregate gets the same bits from
+ * either. BGNN_E_ARG, before anything is launched, when: y or out is NULL; H % 8 != 0 or H > 512;
+ * ldy / ldx / ldo is < H or not a multiple of 8 (4 for an f32 out); exactly one of scale / shift is
+ * NULL; a pointer is not 16-byte aligned. n_rows <= 0 returns BGNN_OK without a launch. */
+int bgnn_sage_tail_bf16(const void* y, int64_t ldy, const float* bias, const float* scale,
+                        const float* shift, const void* x_prev, int64_t ldx, int64_t n_rows,
+                        int32_t H, void* out, int64_t ldo, int32_t out_f32, void* stream);
 
 /* Backward pass 1: BatchNorm statistics of the incoming gradient g (= dL/dx_next):
  *   g2 = relu'(o*scale+shift) * dropout'(g);  partial sums of g2 and g2*xhat.
