@@ -3,29 +3,17 @@
 // finished y = [agg | x] [W_l | W_r]^T). Both compile this one function, with -ffp-contract=off.
 #pragma once
 
-#include "common.h"
-#include "seg_common.h"
+#include "b16_gather.h"   // ld16_nt, store8_nt; common.h and seg_common.h with it
 
 namespace bgnn {
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint4 ld16(const uint16_t* p) { return *reinterpret_cast<const uint4*>(p); }
-
-// stream-once rows (z_r, y, x_prev): non-temporal, so they do not displace gathered rows
-__device__ __forceinline__ uint4 ld16_nt(const uint16_t* p) {
-    const u32x4_t q = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-    return make_uint4(q[0], q[1], q[2], q[3]);
-}
-
-// What the tail reads and writes besides the row's own h terms.
+// What the tail reads and writes besides the row's own h terms. The row width H is its caller's
+// (GatherArgs::H in sage_infer.hip), and so is the name ldx: x_prev's leading dimension is ldxp.
 struct TailArgs {
-    int32_t H;
     const float* bias;
     const float* scale;
     const float* shift;
-    const uint16_t* xprev;  int64_t ldx;    // bf16 [N, H] or NULL
+    const uint16_t* xprev;  int64_t ldxp;   // bf16 [N, H] or NULL
     void* out;              int64_t ldo;
     int32_t out_f32, mean;
 };
@@ -35,8 +23,8 @@ struct Coef {
     float b[512], sc[512], sh[512];
 };
 
-__device__ __forceinline__ void stage_coef(const TailArgs& A, Coef& C) {
-    for (int c = threadIdx.x; c < A.H; c += blockDim.x) {
+__device__ __forceinline__ void stage_coef(const TailArgs& A, int32_t H, Coef& C) {
+    for (int c = threadIdx.x; c < H; c += blockDim.x) {
         C.b[c] = A.bias ? A.bias[c] : 0.f;
         if (A.scale) {
             C.sc[c] = A.scale[c];
@@ -76,17 +64,7 @@ __device__ __forceinline__ void infer_tail(const TailArgs& A, const Coef& C, int
 #pragma unroll
         for (int q = 0; q < 8; ++q) y[q] += xp[q];
     }
-    if (A.out_f32) {
-        float* p = static_cast<float*>(A.out) + r * A.ldo + c;
-        const f32x4_t v0 = {y[0], y[1], y[2], y[3]}, v1 = {y[4], y[5], y[6], y[7]};
-        __builtin_nontemporal_store(v0, reinterpret_cast<f32x4_t*>(p));
-        __builtin_nontemporal_store(v1, reinterpret_cast<f32x4_t*>(p + 4));
-    } else {
-        uint16_t* p = static_cast<uint16_t*>(A.out) + r * A.ldo + c;
-        const u32x4_t v = {bf16_pack2(y[0], y[1]), bf16_pack2(y[2], y[3]), bf16_pack2(y[4], y[5]),
-                           bf16_pack2(y[6], y[7])};
-        __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(p));
-    }
+    store8_nt(A.out, r * A.ldo, c, A.out_f32, y);
 }
 
 }  // namespace bgnn

@@ -14,7 +14,9 @@ namespace bgnn {
 
 namespace {
 
-struct RowTailArgs : TailArgs {
+struct RowTailArgs {
+    int32_t H;
+    TailArgs T;
     const uint16_t* y;      int64_t ldy;    // bf16 [n_rows, H]
     int64_t n_rows;
 };
@@ -32,7 +34,7 @@ __global__ __launch_bounds__(256) void k_tail_row(RowTailArgs A) {
     const bool ok = lane * 8 < A.H;
     const int cs = ok ? lane * 8 : 0;
     __shared__ __attribute__((aligned(16))) Coef C;
-    stage_coef(A, C);
+    stage_coef(A.T, A.H, C);
     const float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int64_t step = (int64_t)gridDim.x * 4;
     for (int64_t r0 = (int64_t)blockIdx.x * 4 + wave; r0 < A.n_rows; r0 += R * step) {
@@ -42,12 +44,12 @@ __global__ __launch_bounds__(256) void k_tail_row(RowTailArgs A) {
             const int64_t rt = r0 + t * step;
             const int64_t rl = rt < A.n_rows ? rt : r0;   // (wave-uniform) past the end: re-read the first row
             yq[t] = ld16_nt(A.y + rl * A.ldy + cs);
-            xq[t] = A.xprev ? ld16_nt(A.xprev + rl * A.ldx + cs) : make_uint4(0, 0, 0, 0);
+            xq[t] = A.T.xprev ? ld16_nt(A.T.xprev + rl * A.T.ldxp + cs) : make_uint4(0, 0, 0, 0);
         }
 #pragma unroll
         for (int t = 0; t < R; ++t) {
             const int64_t rt = r0 + t * step;
-            if (rt < A.n_rows) infer_tail(A, C, rt, 0, a, yq[t], xq[t], cs, ok);
+            if (rt < A.n_rows) infer_tail(A.T, C, rt, 0, a, yq[t], xq[t], cs, ok);
         }
     }
 }
@@ -74,15 +76,15 @@ extern "C" int bgnn_sage_tail_bf16(const void* y, int64_t ldy, const float* bias
 
     RowTailArgs A{};
     A.H = H;
-    A.bias = bias;
-    A.scale = scale;
-    A.shift = shift;
-    A.xprev = static_cast<const uint16_t*>(x_prev);
-    A.ldx = ldx;
-    A.out = out;
-    A.ldo = ldo;
-    A.out_f32 = out_f32 ? 1 : 0;
-    A.mean = 0;
+    A.T.bias = bias;
+    A.T.scale = scale;
+    A.T.shift = shift;
+    A.T.xprev = static_cast<const uint16_t*>(x_prev);
+    A.T.ldxp = ldx;
+    A.T.out = out;
+    A.T.ldo = ldo;
+    A.T.out_f32 = out_f32 ? 1 : 0;
+    A.T.mean = 0;
     A.y = static_cast<const uint16_t*>(y);
     A.ldy = ldy;
     A.n_rows = n_rows;

@@ -1,5 +1,6 @@
-// Helpers shared by the CSR aggregation kernels (spmm.hip, sage_infer.hip, spmm_b16.hip,
-// spmm_max_b16.hip) and the bf16 element-wise kernels (elem.hip): the canonical SAGE row arithmetic,
+// Helpers shared by the CSR aggregation kernels (spmm.hip, and through b16_gather.h the bf16 ones:
+// sage_infer.hip, spmm_b16.hip, spmm_max_b16.hip), the tail (sage_tail.h) and the bf16 element-wise
+// kernels (elem.hip): the canonical SAGE row arithmetic,
 // the XCD sweep's row assignment, a lane's column positions, the MAX argmax state's layout and the
 // bf16 pack / unpack of one 16-byte vector.
 #pragma once
