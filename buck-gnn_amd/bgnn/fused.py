@@ -43,6 +43,10 @@ DGRAD_WT = True
 # both are f32-class, torch.mm saved ~1 % of the step but shifts the BN-amplified gradient
 # rounding noise, tools/fold_ab.py)
 FOLD_WEIGHTS_TORCH = False
+# ... in the grouped native launches of csrc/fold.hip (bgnn_fold_weights_fwd / _bwd: one or two
+# launches per direction instead of ~7, bit-identical to the bgnn_gemm chain, which stays as the
+# fallback for shapes the planner does not put on the 128 x 128 f16x3 tile; A/B switch)
+FOLD_NATIVE = True
 # skip layers' dgrad adds the dropout-masked incoming gradient in its epilogue
 # (bgnn_gemm_f32_dropadd) instead of reading a skip gradient bgnn_sage_bwd_rows wrote
 DGRAD_DROPADD = True
@@ -712,6 +716,15 @@ def _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg: LayerConfig, g_rows=N
     return dgamma, dbeta, z, z
 
 
+def _fold_native_ok(famax, wcat, w_in, b_in) -> bool:
+    """The folded layer's weight products take the grouped native launches (FOLD_NATIVE): the hip
+    backend with its fold_amax slots, row-major operands, and a shape whose five products the GEMM
+    planner puts on the tile csrc/fold.hip regroups."""
+    return bool(FOLD_NATIVE and GEMM_BACKEND == "hip" and famax is not None and famax.is_contiguous()
+                and famax.numel() >= 5 and wcat.stride(1) == 1 and w_in.stride(1) == 1 and b_in.is_contiguous()
+                and _lib.query("bgnn_fold_weights_supported", wcat.size(1), w_in.size(1)))
+
+
 class SageLayerFn(torch.autograd.Function):
     """Outputs (x_next, max|x_next|): the second output (non-differentiable) is the f16x3 GEMM
     operand scale of the next layer, folded in by bgnn_sage_apply at no extra pass.
@@ -750,9 +763,19 @@ class SageLayerFn(torch.autograd.Function):
             # Wf = [W_l;W_r] W_in [2H, K_in], bf = [W_l;W_r] b_in
             if cfg.skip:
                 raise ValueError("sage_layer: a folded input transform needs a layer without skip")
+            wf_t = None
+            fold_native = not FOLD_WEIGHTS_TORCH and _fold_native_ok(cfg.famax, wcat, w_in, b_in)
             if FOLD_WEIGHTS_TORCH:
                 wf = torch.mm(wcat, w_in)
                 bf = torch.mv(wcat, b_in)
+            elif fold_native:
+                K_in = w_in.size(1)
+                wf = torch.empty(2 * H, K_in, dtype=torch.float32, device=dev)
+                bf = torch.empty(2 * H, dtype=torch.float32, device=dev)
+                wf_t = torch.empty(K_in, 2 * H, dtype=torch.float32, device=dev) if DGRAD_WT else None
+                _lib.call("bgnn_fold_weights_fwd", H, K_in, wcat.data_ptr(), wcat.stride(0), w_in.data_ptr(),
+                          w_in.stride(0), b_in.data_ptr(), cfg.famax.data_ptr(), wf.data_ptr(), K_in, bf.data_ptr(),
+                          _ptr(wf_t), 2 * H, w_amax.data_ptr(), _stream())
             else:
                 fs = cfg.famax
                 fa = (fs[0:1], fs[1:2], fs[2:3]) if fs is not None else (None, None, None)
@@ -765,7 +788,8 @@ class SageLayerFn(torch.autograd.Function):
                 # Shared variant 50x further from fp64, tests/test_gpu_fold.py)
                 bf = gemm(wcat, b_in.contiguous().view(H, 1), trans_a=False, trans_b=False, a_amax=fa[0],
                           b_amax=fa[2]).view(-1)
-            absmax(wf, w_amax, accumulate=True)
+            if not fold_native:   # (the native launch folds max|Wf| in itself)
+                absmax(wf, w_amax, accumulate=True)
             wmat = wf
         else:
             if wprep is None:
@@ -821,7 +845,7 @@ class SageLayerFn(torch.autograd.Function):
         ctx.wcat_t = wcat_t_pre
         ctx.img_d = img_d if not folded else None
         ctx.set_materialize_grads(False)   # the amax output never gets a gradient: no zero fill for it
-        ctx.fold = (w_in, b_in, wf) if folded else None
+        ctx.fold = (w_in, b_in, wf, wf_t) if folded else None
         ctx.save_for_backward(x_prev, o, nrm, wcat, gamma if gamma is not None else torch.empty(0, device=dev),
                               scale if scale is not None else torch.empty(0, device=dev),
                               shift if shift is not None else torch.empty(0, device=dev),
@@ -904,8 +928,8 @@ class SageLayerFn(torch.autograd.Function):
         if ctx.folded:
             # x = h W_in^T + b_in folded in: dh = dz Wf; dWf = dz^T h; dbf = column sums of dz;
             # then dWcat = dWf W_in^T + dbf b_in^T (= dz^T x), dW_in = Wcat^T dWf, db_in = Wcat^T dbf
-            w_in, b_in, wf = ctx.fold
-            wf_t = wf.t().contiguous() if DGRAD_WT else wf
+            w_in, b_in, wf, wf_t = ctx.fold
+            wf_t = (wf_t if wf_t is not None else wf.t().contiguous()) if DGRAD_WT else wf
             with _timed("gemm_dgrad_fold"):
                 dx = gemm(dz, wf_t, trans_a=False, trans_b=DGRAD_WT, a_amax=dz_amax, b_amax=w_amax)
             fs = cfg.famax
@@ -914,9 +938,21 @@ class SageLayerFn(torch.autograd.Function):
                 dwf = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax,
                            c_amax=fa[3])                                                   # [2H, K_in]
             dbf = db2.view(-1)                                                              # Σ dz_l ; Σ dh
-            if fs is not None:
+            fold_native = not FOLD_WEIGHTS_TORCH and _fold_native_ok(fs, wcat, w_in, b_in) and dwf.stride(1) == 1
+            if fs is not None and not fold_native:
                 absmax(db2, fa[4], accumulate=True)
-            if FOLD_WEIGHTS_TORCH:
+            if fold_native:   # (max|dbf| folded into fs[4] by the launch itself)
+                K_in = w_in.size(1)
+                dw = torch.empty(2 * H, H, dtype=torch.float32, device=dev)
+                dw_in = torch.empty(H, K_in, dtype=torch.float32, device=dev)
+                db_in = torch.empty(H, dtype=torch.float32, device=dev)
+                ws_bytes = _lib.query("bgnn_fold_weights_ws_bytes", H, K_in)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+                _lib.call("bgnn_fold_weights_bwd", H, K_in, dwf.data_ptr(), dwf.stride(0), dbf.data_ptr(),
+                          wcat.data_ptr(), wcat.stride(0), w_in.data_ptr(), w_in.stride(0), b_in.data_ptr(),
+                          fs.data_ptr(), dw.data_ptr(), H, dw_in.data_ptr(), K_in, db_in.data_ptr(), _ptr(ws),
+                          ws_bytes, s)
+            elif FOLD_WEIGHTS_TORCH:
                 dw = torch.addmm(torch.outer(dbf, b_in), dwf, w_in.t())                    # [2H, H]
                 dw_in = torch.mm(wcat.t(), dwf)                                            # [H, K_in]
                 db_in = torch.mv(wcat.t(), dbf)                                            # [H]

@@ -446,6 +446,23 @@ static Plan make_plan(int64_t M, int64_t N, int64_t K, int ta, int tb, int64_t a
     return p;
 }
 
+// K range per split-K slab: K / split rounded up to whole bk-deep slices
+static int64_t split_kchunk(int64_t K, int split, int bk) {
+    int64_t kc = (K + split - 1) / split;
+    kc = (kc + bk - 1) / bk * bk;
+    return kc > 0 ? kc : bk;
+}
+
+namespace bgnn {
+bool small_h3_plan(int64_t M, int64_t N, int64_t K, int ta, int tb, int* split, int64_t* kchunk) {
+    const Plan p = make_plan(M, N, K, ta, tb, 0, 0);
+    if (!p.x6 || p.prec != 1 || p.cfg != 0) return false;
+    *split = p.split;
+    *kchunk = split_kchunk(K, p.split, p.bk);
+    return true;
+}
+}  // namespace bgnn
+
 // workspace: [256 B operand-max head (f16x3)] [split-K slabs]
 constexpr size_t kAmaxHead = 256;
 
@@ -695,9 +712,7 @@ static int gemm_scaled_impl(int32_t ta, int32_t tb, int64_t M, int64_t N, int64_
     // max |C| for the next GEMM's operand scale: in the split kernels' epilogue, else one pass
     const bool c_amax_fused = c_amax != nullptr && pl.x6 && split == 1;
     if (c_amax_fused) g.c_amax = c_amax;
-    int64_t kc = (K + split - 1) / split;
-    kc = (kc + pl.bk - 1) / pl.bk * pl.bk;
-    g.kchunk = kc > 0 ? kc : pl.bk;
+    g.kchunk = split_kchunk(K, split, pl.bk);
     const int64_t tiles_a = ((Ma + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn);
     dim3 grid((unsigned)tiles_a, split);
     if (pl.x6) launch_x6(pl.prec, ta, tb, pl.cfg, bs.src ? 8 : 0, grid, s, g);

@@ -87,6 +87,10 @@ struct X6Cfg {
 extern const X6Cfg kX6Cfgs[];
 extern const int kNumX6Cfgs;
 void launch_x6(int prec, int ta, int tb, int cfg, int abl, dim3 grid, hipStream_t s, const GemmArgs& g);
+// the plan bgnn_gemm_f32_scaled gives a dense f32-accurate product (gemm.hip): true when it is the
+// f16x3 family's 4-wave 128 x 128 tile (config 0), with its split-K factor and the K range per slab
+// (fold.hip runs the folded layer's weight products on that plan, regrouped)
+bool small_h3_plan(int64_t M, int64_t N, int64_t K, int ta, int tb, int* split, int64_t* kchunk);
 // bf16-operand GEMM on bf16-STORED A and B (gemm_b16.hip): b16_ok = the call qualifies (ta 0,
 // tb 1, storage bits 0 and 1, K % 64 == 0, dense 16-B aligned rows, no split-K / drop-add);
 // launch_b16 covers all M rows (one 256x256 tile per workgroup)

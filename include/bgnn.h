@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 16
+#define BGNN_ABI_VERSION 17
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -628,6 +628,36 @@ int bgnn_absmax_f32(const float* x, int64_t rows, int64_t cols, int64_t ld, floa
  * x 16-B aligned), in one launch (the per-layer weight maxima of a SAGE layer loop). */
 int bgnn_absmax_items_f32(const float* x, int32_t n_items, int64_t item_stride, int64_t rows, int64_t cols,
                           int64_t ld, float* out, int64_t out_stride, void* stream);
+/* The folded first SAGE layer's weight-by-weight products (ABI 17; bgnn/fused.py SageLayerFn with
+ * w_in), each in one grouped launch plus at most one small second launch, no allocation, no host
+ * sync. Wcat = [W_l;W_r] [2H, H], W_in [H, K_in], b_in [H]; all matrices row-major with leading
+ * dimensions in elements. fold_amax: 5 device slots holding non-negative values (zeroed per step):
+ * max|Wcat|, max|W_in|, max|b_in|, max|dWf|, max|dbf| -- the f16x3 operand scales.
+ *   bgnn_fold_weights_fwd  folds max|Wcat|, max|W_in|, max|b_in| into slots 0-2, then
+ *     Wf = Wcat W_in [2H, K_in], bf = Wcat b_in [2H], Wf^T into wf_t [K_in, 2H] (NULL: not written)
+ *     and max|Wf| folded into *w_amax (unsigned atomic max on the f32 bits).
+ *   bgnn_fold_weights_bwd  reads slots 0, 1, 3 (max|dWf| from the weight-gradient GEMM), folds
+ *     max|dbf| into slot 4, then dWcat = dWf W_in^T + dbf (x) b_in [2H, H] (the outer product and
+ *     the sum each rounded once), dW_in = Wcat^T dWf [H, K_in], db_in = Wcat^T dbf [H].
+ *     ws: bgnn_fold_weights_ws_bytes(H, K_in) bytes (the slabs of the products the planner splits
+ *     along K; may be 0 / NULL).
+ * Every output element has the bits bgnn_gemm_f32_scaled gives for the same product with the same
+ * maxima (same scales, piece split, MFMA shape, k order, slab order, epilogue arithmetic).
+ * bgnn_fold_weights_supported: 1 for exactly the shapes both entry points accept: the planner runs
+ * all five products on the f16x3 family's 4-wave 128 x 128 tile with fewer than 16 slabs, and does
+ * not split Wf, bf or dWcat along K (else 0: use the GEMMs). The planned workspace is required in
+ * full (bgnn_gemm_f32_scaled would drop to one slab on a short one). BGNN_E_ARG, before
+ * anything is launched: a NULL pointer, H or K_in <= 0, a leading dimension shorter than its row,
+ * an unsupported shape, a workspace smaller than asked. */
+int32_t bgnn_fold_weights_supported(int64_t H, int64_t K_in);
+size_t bgnn_fold_weights_ws_bytes(int64_t H, int64_t K_in);
+int bgnn_fold_weights_fwd(int64_t H, int64_t K_in, const float* wcat, int64_t ld_wcat, const float* w_in,
+                          int64_t ld_win, const float* b_in, float* fold_amax, float* wf, int64_t ld_wf,
+                          float* bf, float* wf_t, int64_t ld_wft, float* w_amax, void* stream);
+int bgnn_fold_weights_bwd(int64_t H, int64_t K_in, const float* dwf, int64_t ld_dwf, const float* dbf,
+                          const float* wcat, int64_t ld_wcat, const float* w_in, int64_t ld_win,
+                          const float* b_in, float* fold_amax, float* dwcat, int64_t ld_dwcat, float* dw_in,
+                          int64_t ld_dwin, float* db_in, void* ws, size_t ws_bytes, void* stream);
 int bgnn_gemm_f32_planes(int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t K,
                          float alpha, const float* A, int64_t lda, int64_t a_blk, int64_t a_pstride,
                          const float* B, int64_t ldb, float beta, float* C, int64_t ldc,
