@@ -880,6 +880,8 @@ extern "C" int bgnn_sage_apply(const float* o, const float* scale, const float* 
                                int32_t skip, float p, uint64_t seed, int64_t n_rows, int32_t H, float* x_next,
                                float* amax, const int32_t* ranges, float* range_partial, void* stream) {
     BGNN_REQUIRE(H > 0 && H % 4 == 0, "sage_apply: H must be a multiple of 4");
+    BGNN_REQUIRE(n_rows >= 0, "sage_apply: negative n_rows");
+    BGNN_REQUIRE(n_rows == 0 || (o && x_next), "sage_apply: null o / x_next");
     BGNN_REQUIRE(p >= 0.f && p < 1.f, "sage_apply: dropout p must be in [0, 1)");
     BGNN_REQUIRE((scale == nullptr) == (shift == nullptr), "sage_apply: scale/shift must both be set or NULL");
     BGNN_REQUIRE(!skip || x_prev, "sage_apply: skip requires x_prev");
@@ -929,6 +931,7 @@ extern "C" int bgnn_sage_bwd_stats(const float* g, const int64_t* g_rows, const 
                                    const float* mean, const float* invstd, float p, uint64_t seed, int64_t n_rows,
                                    int32_t H, float* partial2, void* stream) {
     BGNN_REQUIRE(H > 0 && H % 4 == 0 && H <= 1024, "sage_bwd_stats: H=%d unsupported", H);
+    BGNN_REQUIRE(n_rows >= 0, "sage_bwd_stats: negative n_rows");
     BGNN_REQUIRE(g && o && scale && shift && mean && invstd && partial2, "sage_bwd_stats: null pointer");
     BGNN_REQUIRE(al16(g) && al16(o) && al16(scale) && al16(shift) && al16(mean) && al16(invstd) && al16(partial2),
                  "sage_bwd_stats: pointers must be 16-byte aligned");
@@ -952,6 +955,8 @@ extern "C" int bgnn_sage_bwd_rows(const float* g, const int64_t* g_rows, const f
                                   const int32_t* ranges, const int32_t* range_w_rowptr, float* range_partial,
                                   void* stream) {
     BGNN_REQUIRE(H > 0 && H % 4 == 0 && H <= 512, "sage_bwd_rows: H=%d unsupported", H);
+    BGNN_REQUIRE(n_rows >= 0, "sage_bwd_rows: negative n_rows");
+    BGNN_REQUIRE(g && o && nrm && dh && partial_db, "sage_bwd_rows: null pointer");
     BGNN_REQUIRE(w_mode >= 0 && w_mode <= 2 && (w_mode == 0 || w_rowptr), "sage_bwd_rows: bad row weights");
     BGNN_REQUIRE(lddh >= H && lddh % 4 == 0, "sage_bwd_rows: bad lddh");
     BGNN_REQUIRE(!skip || gskip, "sage_bwd_rows: skip requires gskip");
@@ -989,6 +994,7 @@ extern "C" int bgnn_sage_bwd_rows(const float* g, const int64_t* g_rows, const f
 extern "C" int bgnn_l2norm_bwd(const float* g, const float* o, const float* nrm, int64_t n_rows, int32_t H,
                                float* dh, int64_t lddh, float* partial_db, float* amax, void* stream) {
     BGNN_REQUIRE(H > 0 && H % 4 == 0 && H <= 512, "l2norm_bwd: H=%d unsupported", H);
+    BGNN_REQUIRE(n_rows >= 0, "l2norm_bwd: negative n_rows");
     BGNN_REQUIRE(g && o && nrm && dh && partial_db && amax, "l2norm_bwd: null pointer");
     BGNN_REQUIRE(lddh >= H && lddh % 4 == 0, "l2norm_bwd: bad lddh");
     BGNN_REQUIRE(al16(g) && al16(o) && al16(dh) && al16(partial_db), "l2norm_bwd: pointers must be 16-byte aligned");

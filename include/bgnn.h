@@ -308,7 +308,11 @@ int bgnn_sage_apply(const float* o, const float* scale, const float* shift,
                     const int32_t* ranges, float* range_partial, void* stream);
 /* ranges (optional, the next layer's forward-CSR bgnn_heavy_ranges buffer): also the range
  * partials of x_next (bgnn_range_partial_bytes; finish with bgnn_range_sums_finish mode 0), by a
- * row-blocked form of the same element-wise pass (the same x_next bits). */
+ * row-blocked form of the same element-wise pass (the same x_next bits).
+ * BGNN_E_ARG, before anything is launched, when: n_rows < 0; o or x_next is NULL with n_rows > 0;
+ * H % 4 != 0 (ranges: H > 512); p outside [0, 1); exactly one of scale / shift is NULL; skip
+ * without x_prev; ranges without range_partial; a pointer is not 16-byte aligned. n_rows == 0
+ * returns BGNN_OK without a launch. */
 
 /* Eval-mode SAGE layer on bf16 rows (ABI 14): the aggregation of bgnn_sage_fwd and the tail of
  * bgnn_sage_apply (no dropout) in one pass over z = x [W_l ; W_r]^T stored as bf16 [N, 2H]
@@ -404,7 +408,9 @@ int bgnn_sage_tail_bf16(const void* y, int64_t ldy, const float* bias, const flo
  *   g2 = relu'(o*scale+shift) * dropout'(g);  partial sums of g2 and g2*xhat.
  * g_rows (ABI 13; NULL: g is [n_rows, H]): row r's gradient is row g_rows[r] of g -- the last
  * layer under a mean pool (Models/BuckGNN.py:246-249 global_mean_pool) reads the pooled gradient
- * [graphs, H] / count through the batch vector instead of a materialised [N, H] broadcast. */
+ * [graphs, H] / count through the batch vector instead of a materialised [N, H] broadcast.
+ * BGNN_E_ARG, before anything is launched, when: n_rows < 0; H % 4 != 0 or H > 1024; g, o, scale,
+ * shift, mean, invstd or partial2 is NULL or not 16-byte aligned. */
 int32_t bgnn_rows_slots(int64_t n_rows);
 int bgnn_sage_bwd_stats(const float* g, const int64_t* g_rows, const float* o, const float* scale,
                         const float* shift,
@@ -441,7 +447,11 @@ int bgnn_reduce_partials(const float* partial, int32_t n_slots, int32_t H,
  * the layer's reduce (1 for sum, 2 for mean) that is the column sum of dz_l = A^T dh, the bias
  * gradient of a Linear folded into the layer (fused.sage_layer w_in).
  * sum_g2 / sum_g2xhat are the reduced stats of pass 1 (NULL when BatchNorm is off).
- * amax (optional): *amax = max(*amax, max |dh|). g_rows: as for bgnn_sage_bwd_stats. */
+ * amax (optional): *amax = max(*amax, max |dh|). g_rows: as for bgnn_sage_bwd_stats.
+ * BGNN_E_ARG, before anything is launched, when: n_rows < 0; g, o, nrm, dh or partial_db is NULL;
+ * H % 4 != 0 or H > 512; lddh < H or lddh % 4 != 0; skip without gskip; mean without invstd,
+ * sum_g2 and sum_g2xhat; w_mode outside 0..2 or non-zero without w_rowptr; ranges without
+ * range_partial; g, o, dh, gskip, partial_db or range_partial not 16-byte aligned. */
 int bgnn_sage_bwd_rows(const float* g, const int64_t* g_rows, const float* o, const float* nrm,
                        const float* scale, const float* shift, const float* gamma,
                        const float* mean, const float* invstd,
@@ -461,7 +471,9 @@ int bgnn_sage_bwd_rows(const float* g, const int64_t* g_rows, const float* o, co
  * BatchNorm/ReLU/Dropout. dh = (g - o <o, g>) / ||h|| per row (g * 1e12 where ||h|| < 1e-12),
  * dh row stride lddh; partial_db [bgnn_rows_slots(n_rows)][2][H]: [.][0] = column sums of dh
  * (the lin_l bias gradient; reduce with bgnn_reduce_partials), [.][1] = 0; *amax = max(*amax,
- * max |dh|). nrm is bgnn_sage_fwd's row-norm output. */
+ * max |dh|). nrm is bgnn_sage_fwd's row-norm output. BGNN_E_ARG, before anything is launched,
+ * when: n_rows < 0; a pointer is NULL; H % 4 != 0 or H > 512; lddh < H or lddh % 4 != 0; g, o, dh
+ * or partial_db not 16-byte aligned. */
 int bgnn_l2norm_bwd(const float* g, const float* o, const float* nrm, int64_t n_rows, int32_t H,
                     float* dh, int64_t lddh, float* partial_db, float* amax, void* stream);
 
