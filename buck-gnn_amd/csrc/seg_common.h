@@ -55,6 +55,11 @@ __device__ __forceinline__ Sweep sweep_rows(int64_t n_rows, int wave) {
 // rows hold kArgHeavy), then heavy_of int32 [rows], then arg_h int32 [n_heavy, H], each 256-byte
 // aligned.
 constexpr uint8_t kArgHeavy = 255;
+// The offset a writer stores for a column of a row with deg > 0: g = the winner's CSR position, or
+// -1 when no edge won (every neighbour -inf or NaN: the strict > never fires). Such a column takes
+// offset 0, the row's first edge, so every stored offset is in [0, deg) and the backward never
+// takes a light row for a heavy one (include/bgnn.h, the MAX argmax state).
+__device__ __forceinline__ int32_t arg_offset(int32_t g, int32_t rb) { return g < 0 ? 0 : g - rb; }
 struct MaxArgLayout {
     int64_t heavy_of, arg_h;
 };

@@ -307,7 +307,7 @@ __device__ __forceinline__ void store_plain(const SegArgs& A, Acc<VEC, NV, OP>& 
                 uint32_t w = 0;
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
-                    const uint32_t o = h >= 0 ? kArgHeavy : (deg > 0 ? (uint32_t)(acc.g[v][k] - rb) : 0u);
+                    const uint32_t o = h >= 0 ? kArgHeavy : (deg > 0 ? (uint32_t)arg_offset(acc.g[v][k], rb) : 0u);
                     w |= (o & 0xffu) << (8 * k);
                 }
                 if constexpr (VEC == 4) *reinterpret_cast<uint32_t*>(A.arg8 + r * A.H + cpos[v]) = w;
@@ -315,7 +315,7 @@ __device__ __forceinline__ void store_plain(const SegArgs& A, Acc<VEC, NV, OP>& 
                 if (h >= 0) {
                     int32_t gi[VEC];
 #pragma unroll
-                    for (int k = 0; k < VEC; ++k) gi[k] = acc.g[v][k] - rb;
+                    for (int k = 0; k < VEC; ++k) gi[k] = arg_offset(acc.g[v][k], rb);
                     sti<VEC>(A.arg_h + (int64_t)h * A.H + cpos[v], gi);
                 }
             }
@@ -1188,6 +1188,18 @@ inline SegArgs args_from_csr(const bgnn_csr_t* c) {
     return A;
 }
 
+// The operand checks of bgnn_spmm_fwd and the transposes, after their own: nothing is launched on a
+// CSR or an operand that a kernel would dereference as NULL. xn / on: the source / result names.
+inline int check_plain(const char* name, const char* xn, const char* on, const bgnn_csr_t* c, const void* x,
+                       const void* out) {
+    BGNN_REQUIRE(c->n_rows >= 0, "%s: negative n_rows", name);
+    BGNN_REQUIRE(c->n_rows == 0 || (x && out), "%s: null %s / %s", name, xn, on);
+    BGNN_REQUIRE(c->nnz <= 0 || c->col, "%s: null col", name);
+    BGNN_REQUIRE(c->n_chunks <= 0 || (c->heavy_row && c->heavy_chunk0 && c->chunk_heavy),
+                 "%s: heavy rows need the CSR's chunk plan", name);
+    return BGNN_OK;
+}
+
 extern int g_x6_bdma;   // gemm_x6.hip
 extern int g_h3p_nsb;   // gemm_h3p.hip
 #ifdef BGNN_H3P_ABLATION
@@ -1205,6 +1217,7 @@ extern "C" int bgnn_spmm_fwd(const bgnn_csr_t* csr, const float* x, int64_t ldx,
     BGNN_REQUIRE(H > 0 && ldx >= H && ldo >= H, "spmm_fwd: bad H/ld");
     BGNN_REQUIRE(reduce >= 0 && reduce <= 2, "spmm_fwd: bad reduce %d", reduce);
     BGNN_REQUIRE(csr->n_chunks == 0 || partial, "spmm_fwd: partial scratch required for heavy rows");
+    if (const int rc = check_plain("spmm_fwd", "x", "out", csr, x, out)) return rc;
     SegArgs A = args_from_csr(csr);
     g_heavy_dir = 0;
     A.H = H;
@@ -1223,6 +1236,7 @@ extern "C" int bgnn_spmm_fwd(const bgnn_csr_t* csr, const float* x, int64_t ldx,
         A.heavy_of = reinterpret_cast<int32_t*>(static_cast<char*>(arg) + L.heavy_of);
         A.arg_h = reinterpret_cast<int32_t*>(static_cast<char*>(arg) + L.arg_h);
     }
+    if (csr->n_rows == 0) return BGNN_OK;   // nothing to write, nothing launched
     A.partial = partial;
     A.partial_arg = partial ? reinterpret_cast<int32_t*>(partial + (int64_t)csr->n_chunks * H) : nullptr;
     const bool al = aligned16(x) && aligned16(out) && ldx % 4 == 0 && ldo % 4 == 0 &&
@@ -1275,6 +1289,11 @@ static int spmm_bwd_impl(const bgnn_csr_t* csr_t, const int32_t* perm_t, const i
     BGNN_REQUIRE(!addend || ld_add >= H, "spmm_bwd: bad ld_add");
     BGNN_REQUIRE(H > 0 && ldg >= H && ldgx >= H, "spmm_bwd: bad H/ld");
     BGNN_REQUIRE(csr_t->n_chunks == 0 || partial, "spmm_bwd: partial scratch required");
+    if (const int rc = check_plain("spmm_bwd", "g", "gx", csr_t, g, gx)) return rc;
+    BGNN_REQUIRE(reduce != BGNN_REDUCE_MEAN || fwd_rowptr, "spmm_bwd(mean): fwd_rowptr required");
+    BGNN_REQUIRE(reduce == BGNN_REDUCE_SUM || reduce == BGNN_REDUCE_MEAN || (perm_t && arg && fwd_rowptr),
+                 "spmm_bwd(max): perm_t, fwd_rowptr and arg required");
+    if (csr_t->n_rows == 0) return BGNN_OK;   // nothing to write, nothing launched
     SegArgs A = args_from_csr(csr_t);
     g_heavy_dir = 1;
     A.H = H;
@@ -1300,12 +1319,8 @@ static int spmm_bwd_impl(const bgnn_csr_t* csr_t, const int32_t* perm_t, const i
     hipStream_t s = as_stream(stream);
     switch (reduce) {
         case BGNN_REDUCE_SUM: return dispatch_plain<OP_SUM>(A, geo, s);
-        case BGNN_REDUCE_MEAN:
-            BGNN_REQUIRE(fwd_rowptr, "spmm_bwd(mean): fwd_rowptr required");
-            return dispatch_plain<OP_MEANT>(A, geo, s);
-        default:
-            BGNN_REQUIRE(perm_t && arg && fwd_rowptr, "spmm_bwd(max): perm_t, fwd_rowptr and arg required");
-            return dispatch_plain<OP_MAXT>(A, geo, s);
+        case BGNN_REDUCE_MEAN: return dispatch_plain<OP_MEANT>(A, geo, s);
+        default: return dispatch_plain<OP_MAXT>(A, geo, s);
     }
 }
 

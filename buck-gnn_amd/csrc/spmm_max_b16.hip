@@ -54,15 +54,15 @@ __device__ __forceinline__ void store_row(const MaxArgs& A, int64_t r, int32_t d
         uint32_t w[2] = {0u, 0u};
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const uint32_t o = h >= 0 ? kArgHeavy : (deg > 0 ? (uint32_t)(g[q] - rb) : 0u);
+            const uint32_t o = h >= 0 ? kArgHeavy : (deg > 0 ? (uint32_t)arg_offset(g[q], rb) : 0u);
             w[q >> 2] |= (o & 0xffu) << (8 * (q & 3));
         }
         const u32x2_t wv = {w[0], w[1]};
         *reinterpret_cast<u32x2_t*>(A.arg8 + r * A.H + c) = wv;
         if (h >= 0) {
             int4* p = reinterpret_cast<int4*>(A.arg_h + (int64_t)h * A.H + c);
-            p[0] = make_int4(g[0] - rb, g[1] - rb, g[2] - rb, g[3] - rb);
-            p[1] = make_int4(g[4] - rb, g[5] - rb, g[6] - rb, g[7] - rb);
+            p[0] = make_int4(arg_offset(g[0], rb), arg_offset(g[1], rb), arg_offset(g[2], rb), arg_offset(g[3], rb));
+            p[1] = make_int4(arg_offset(g[4], rb), arg_offset(g[5], rb), arg_offset(g[6], rb), arg_offset(g[7], rb));
         }
     }
 }

@@ -149,7 +149,9 @@ size_t bgnn_graph_build_ws_bytes(int64_t num_edges, int64_t num_nodes);
  *   forward CSR (rows = targets):   rowptr[N+1], col[E] = sources,
  *   transpose CSR (rows = sources): rowptr_t[N+1], col_t[E] = targets,
  *                                   perm_t[E] = forward-CSR position of the edge.
- * Both sorts are stable, so entries of a row keep edge_index order.
+ * Both sorts are stable: the forward CSR sorts edge_index by target, so entries of a row keep
+ * edge_index order; the transpose sorts the forward CSR's entries by source, so a transposed row
+ * lists its entries in forward-CSR order (perm_t increases along it).
  * `dev_status` (device int32, may be NULL) receives 0, or 1 if an index was outside
  * [0, N). Fully asynchronous: no host synchronisation. */
 int bgnn_graph_build(const int64_t* edge_index, int64_t num_edges, int64_t num_nodes,
@@ -234,7 +236,22 @@ int bgnn_spmm_fwd(const bgnn_csr_t* csr, const float* x, int64_t ldx, int32_t H,
  * plus the int32 offset in a per-heavy-row array -- 1 B instead of 4 B per element written by the
  * forward and gathered per edge by the backward. Ties: the first maximising edge in CSR order.
  * Requires csr->chunk in [1, 254] when arg != NULL (BGNN_E_ARG otherwise: a larger chunk would
- * let a light row's offset reach the marker); the library's plans use chunk 64. */
+ * let a light row's offset reach the marker); the library's plans use chunk 64.
+ * Values: the accumulator starts at -inf and an edge replaces it only when strictly greater, so a
+ * NaN never wins, a column whose neighbours are all -inf or NaN gives -inf, and empty rows give 0.
+ * State contract: after the call every row with deg > 0 holds a valid state in every column -- a
+ * light row a byte offset in [0, deg), a heavy row the marker in every column, heavy_of[row] = its
+ * heavy index and an int32 offset in [0, deg). A column that no edge won (all -inf / NaN) holds
+ * offset 0, the row's first edge in CSR order: "the first maximising edge" of an all -inf column,
+ * and the edge bgnn_spmm_bwd_max then routes the gradient to. Empty rows hold offset 0 and receive
+ * no gradient (they have no edge).
+ * BGNN_E_ARG, before anything is launched, when: csr or csr->rowptr is NULL; H <= 0, ldx < H or
+ * ldo < H; reduce is not SUM / MEAN / MAX; the CSR has chunks and partial is NULL or a pointer of
+ * the chunk plan (heavy_row, heavy_chunk0, chunk_heavy) is NULL; n_rows < 0; x or out is NULL with
+ * n_rows > 0; col is NULL with nnz > 0; arg with a chunk outside [1, 254]. n_rows == 0 returns
+ * BGNN_OK without a launch. Pointers need no alignment: float4 kernels run when x, out, partial
+ * and arg are 16-byte aligned and H, ldx, ldo are multiples of 4, scalar ones otherwise (the same
+ * results). */
 size_t bgnn_spmm_max_arg_bytes(int64_t n_rows, int32_t H, int32_t n_heavy);
 
 /* Backward of bgnn_spmm_fwd through the transpose CSR (rows = sources):
@@ -259,7 +276,13 @@ int bgnn_spmm_bwd_add(const bgnn_csr_t* csr_t, const int32_t* perm_t, const int3
  * (i, c) -- fwd CSR position perm_t[q] == fwd_rowptr[i] + offset in the argmax state `arg` of the
  * forward (fwd_rows = its row count) -- of g[i, c], plus the optional addend (the max-aggregation
  * SAGEConv backward adds the lin_r input gradient dh W_r (+ the skip gradient) this way,
- * bgnn/fused.py). */
+ * bgnn/fused.py).
+ * The three transposes answer BGNN_E_ARG, before anything is launched, when: csr_t or its rowptr
+ * is NULL; H <= 0, ldg < H or ldgx < H; an addend with ld_add < H (0 = not given); the CSR has
+ * chunks and partial is NULL or a pointer of the chunk plan is NULL; n_rows < 0; g or gx is NULL
+ * with n_rows > 0; col is NULL with nnz > 0; reduce is MAX in bgnn_spmm_bwd / bgnn_spmm_bwd_add;
+ * heavy_done without csr_t->ranges; MEAN without fwd_rowptr; bgnn_spmm_bwd_max without perm_t,
+ * fwd_rowptr or arg, or with fwd_rows < 0. n_rows == 0 returns BGNN_OK without a launch. */
 int bgnn_spmm_bwd_max(const bgnn_csr_t* csr_t, const int32_t* perm_t, const int32_t* fwd_rowptr,
                       int64_t fwd_rows, const float* g, int64_t ldg, int32_t H, const void* arg,
                       const float* addend, int64_t ld_add, float* gx, int64_t ldgx, float* partial,
@@ -366,8 +389,10 @@ int bgnn_spmm_bwd_bf16(const bgnn_csr_t* csr_t, const int32_t* fwd_rowptr, const
  *   out[r, :] = max_{e in row r} x[col[e], :]
  * x: bf16 [*, ldx]; out: bf16 [n_rows, ldo]; ld* in elements. The semantics are exactly those of
  * bgnn_spmm_fwd(MAX) on the upcast input: the accumulator starts at -inf, an edge replaces it only
- * when strictly greater (the first maximising edge in CSR order wins, a NaN never wins), empty rows
- * give 0. The maximum of bf16 values is one of them, so nothing is rounded: the result equals the
+ * when strictly greater (the first maximising edge in CSR order wins, a NaN never wins; a column
+ * whose neighbours are all -inf or NaN gives -inf), empty rows give 0. With arg the state contract is
+ * bgnn_spmm_fwd's: every row with deg > 0 holds an offset in [0, deg) in every column (heavy rows: the
+ * marker, heavy_of and an int32 offset in [0, deg)), and a column no edge won holds offset 0. The maximum of bf16 values is one of them, so nothing is rounded: the result equals the
  * f32 kernel's, value for value. A source row is one 16-byte load per lane (8 lines of 128 B at
  * H = 512, the f32 kernel reads 16). x and out may be column planes of one wider allocation
  * (ldx = ldo = 2H: out = plane 0, x = plane 1 of a [N, 2H] buffer).

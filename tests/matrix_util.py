@@ -1,0 +1,100 @@
+"""The window machinery of the GPU conformance matrices (tests/test_gpu_sage_rows_matrix.py,
+tests/test_gpu_spmm_matrix.py): outputs as NaN-filled windows inside guarded allocations, inputs
+with NaN after their last row, the comparison against an fp64 reference under a per-element bound
+with the largest err / bound kept per section, and the amax check."""
+import torch
+
+from sage_rows_ref import D, ratio
+
+PATTERN = 0x4B1D5EED    # guard bit pattern (as f32: 1.03e7, finite)
+NAN = float("nan")
+RATIOS = {}             # section -> largest err / bound seen
+
+
+def ceil4(x):
+    return (x + 3) // 4 * 4
+
+
+class Out:
+    """A rows x cols f32 output window (row stride ld) inside a guarded allocation: two guard rows
+    above and below and the ld padding hold PATTERN; the window starts as NaN or as `init`."""
+
+    def __init__(self, dev, rows, cols, ld=None, init=None):
+        self.rows, self.cols = rows, cols
+        self.ld = ld = ceil4(cols) + 4 if ld is None else ld
+        off = 2 * ld
+        self.idx = (off + torch.arange(rows).view(rows, 1) * ld + torch.arange(cols).view(1, cols)).to(dev)
+        self.buf = torch.empty((rows + 4) * ld, dtype=torch.float32, device=dev)
+        self.buf.view(torch.int32).fill_(PATTERN)
+        self.buf[self.idx] = NAN if init is None else init.to(dev).view(rows, cols)
+        self.ptr = self.buf.data_ptr() + 4 * off
+
+    def read(self):
+        return self.buf[self.idx].cpu()
+
+    def guard(self, label):
+        g = self.buf.view(torch.int32).clone()
+        g[self.idx] = PATTERN
+        bad = (g != PATTERN).nonzero().flatten()
+        assert bad.numel() == 0, (f"{label}: {bad.numel()} guard elements outside the {self.rows} x {self.cols} "
+                                  f"window (ld {self.ld}) overwritten; first at flat offset {int(bad[0])}")
+
+
+def scalar(dev, v):
+    return Out(dev, 1, 1, init=torch.tensor([float(v)]))
+
+
+def inp(dev, t, pad=2):
+    """an input on the device with NaN after its last row (float) -- a read past n_rows poisons"""
+    if t is None:
+        return None
+    if not t.is_floating_point():
+        return t.to(dev)
+    t2 = t.view(t.size(0), -1)
+    buf = torch.full((t2.size(0) + pad, t2.size(1)) if t.dim() > 1 else (t.numel() + 8,), NAN)
+    buf.view(-1)[:t.numel()] = t.reshape(-1)
+    return buf.to(dev)
+
+
+class In:
+    """An f32 [rows, cols] input with row stride ld >= cols: NaN in the ld padding, in two rows after
+    the last one and in `lead` floats before the first (lead = 1: a base pointer 4 bytes past a 16-byte
+    boundary) -- a read outside the rows' columns poisons."""
+
+    def __init__(self, dev, t, ld=None, lead=0):
+        rows, cols = t.shape
+        self.ld = ld = ceil4(cols) + 4 if ld is None else ld
+        host = torch.full((4 + lead + (rows + 2) * ld,), NAN)
+        host[4 + lead:4 + lead + rows * ld].view(rows, ld)[:, :cols] = t
+        self.buf = host.to(dev)
+        self.ptr = self.buf.data_ptr() + 4 * (4 + lead)
+
+
+def ptr(t):
+    return None if t is None else (t.ptr if hasattr(t, "ptr") else t.data_ptr())
+
+
+def check(sec, out, ref, bound, label):
+    fin = torch.isfinite(out)
+    assert bool(fin.all()), f"{label}: {int((~fin).sum())} elements not finite (never written, or a read past an " \
+                            f"input's end); first at {(~fin).nonzero()[0].tolist()}"
+    err = (out.to(D) - ref).abs()
+    r = ratio(err, bound)
+    RATIOS[sec] = max(RATIOS.get(sec, 0.0), r)
+    over = err - bound
+    if bool((over > 0).any()):
+        i = (over.view(-1).argmax()).item()
+        raise AssertionError(f"{label}: {int((over > 0).sum())} elements over the bound (err / bound {r:.3f}); worst "
+                             f"at flat {i}: got {out.view(-1)[i].item():.9g}, fp64 {ref.reshape(-1)[i].item():.9g}, "
+                             f"|err| {err.view(-1)[i].item():.3g} > {bound.reshape(-1)[i].item():.3g}")
+
+
+def amax_prev(i):
+    """alternate: a previous value of 0, and one above every maximum"""
+    return 0.0 if i % 2 == 0 else 3.0e30
+
+
+def check_amax(am, prev, out, label):
+    am.guard(label + " amax")
+    want = max(torch.tensor(prev, dtype=torch.float32).item(), out.abs().max().item() if out.numel() else 0.0)
+    assert am.read().item() == want, f"{label}: amax {am.read().item()!r} != max(previous {prev}, max |output|) = {want!r}"

@@ -25,16 +25,14 @@ import torch
 import sage_rows_ref as R
 from bgnn import _lib
 from bgnn.graph import Csr, _stream
+from matrix_util import RATIOS, Out, amax_prev, check, check_amax, inp, ptr, scalar
 from test_gpu_spmm_b16 import graph_case
 
 pytestmark = pytest.mark.gpu
 
-PATTERN = 0x4B1D5EED    # guard bit pattern (as f32: 1.03e7, finite)
-NAN = float("nan")
 D = torch.float64
 KNOBS = (1, 3, 13)      # BGNN_TUNE_SEG_KERNEL, BGNN_TUNE_SEG_U, BGNN_TUNE_ROWS_REV
 _defaults = {}
-RATIOS = {}
 
 
 @pytest.fixture(autouse=True)
@@ -57,81 +55,6 @@ def _print_ratios():
     print("\nsection: largest err / bound")
     for k in sorted(RATIOS):
         print(f"  {k}: {RATIOS[k]:.3f}")
-
-
-def ceil4(x):
-    return (x + 3) // 4 * 4
-
-
-class Out:
-    """A rows x cols f32 output window (row stride ld) inside a guarded allocation: two guard rows
-    above and below and the ld padding hold PATTERN; the window starts as NaN or as `init`."""
-
-    def __init__(self, dev, rows, cols, ld=None, init=None):
-        self.rows, self.cols = rows, cols
-        self.ld = ld = ceil4(cols) + 4 if ld is None else ld
-        off = 2 * ld
-        self.idx = (off + torch.arange(rows).view(rows, 1) * ld + torch.arange(cols).view(1, cols)).to(dev)
-        self.buf = torch.empty((rows + 4) * ld, dtype=torch.float32, device=dev)
-        self.buf.view(torch.int32).fill_(PATTERN)
-        self.buf[self.idx] = NAN if init is None else init.to(dev).view(rows, cols)
-        self.ptr = self.buf.data_ptr() + 4 * off
-
-    def read(self):
-        return self.buf[self.idx].cpu()
-
-    def guard(self, label):
-        g = self.buf.view(torch.int32).clone()
-        g[self.idx] = PATTERN
-        bad = (g != PATTERN).nonzero().flatten()
-        assert bad.numel() == 0, (f"{label}: {bad.numel()} guard elements outside the {self.rows} x {self.cols} "
-                                  f"window (ld {self.ld}) overwritten; first at flat offset {int(bad[0])}")
-
-
-def scalar(dev, v):
-    return Out(dev, 1, 1, init=torch.tensor([float(v)]))
-
-
-def inp(dev, t, pad=2):
-    """an input on the device with NaN after its last row (float) -- a read past n_rows poisons"""
-    if t is None:
-        return None
-    if not t.is_floating_point():
-        return t.to(dev)
-    t2 = t.view(t.size(0), -1)
-    buf = torch.full((t2.size(0) + pad, t2.size(1)) if t.dim() > 1 else (t.numel() + 8,), NAN)
-    buf.view(-1)[:t.numel()] = t.reshape(-1)
-    return buf.to(dev)
-
-
-def ptr(t):
-    return None if t is None else (t.ptr if isinstance(t, Out) else t.data_ptr())
-
-
-def check(sec, out, ref, bound, label):
-    fin = torch.isfinite(out)
-    assert bool(fin.all()), f"{label}: {int((~fin).sum())} elements not finite (never written, or a read past an " \
-                            f"input's end); first at {(~fin).nonzero()[0].tolist()}"
-    err = (out.to(D) - ref).abs()
-    r = R.ratio(err, bound)
-    RATIOS[sec] = max(RATIOS.get(sec, 0.0), r)
-    over = err - bound
-    if bool((over > 0).any()):
-        i = (over.view(-1).argmax()).item()
-        raise AssertionError(f"{label}: {int((over > 0).sum())} elements over the bound (err / bound {r:.3f}); worst "
-                             f"at flat {i}: got {out.view(-1)[i].item():.9g}, fp64 {ref.reshape(-1)[i].item():.9g}, "
-                             f"|err| {err.view(-1)[i].item():.3g} > {bound.reshape(-1)[i].item():.3g}")
-
-
-def amax_prev(i):
-    """alternate: a previous value of 0, and one above every maximum"""
-    return 0.0 if i % 2 == 0 else 3.0e30
-
-
-def check_amax(am, prev, out, label):
-    am.guard(label + " amax")
-    want = max(torch.tensor(prev, dtype=torch.float32).item(), out.abs().max().item() if out.numel() else 0.0)
-    assert am.read().item() == want, f"{label}: amax {am.read().item()!r} != max(previous {prev}, max |output|) = {want!r}"
 
 
 def slots_sum(part, S, H, label):
