@@ -327,7 +327,9 @@ class BuckGNN(nn.Module):
     def _sage_loop(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, skip_last_excluded: bool,
                    x_amax: Optional[Tensor] = None, x_in: Optional[nn.Linear] = None, pool=None):
         """The SAGE layer loop; pool (a SegmentIndex; fused sum / mean loop only): returns
-        (x, mean pool of x per segment) from the last fused layer instead of x."""
+        (x, mean pool of x per segment) from the last fused layer instead of x. The caller reads
+        only the pool: the last fused layer sums it inside its apply pass and does not store x
+        (need_x=False; x is then None)."""
         L = len(convs) if convs is not None else self.num_layers
         p = self.dropout.p
         if x_in is None and self._infer_bf16_on(x, aggr, bns):
@@ -360,7 +362,7 @@ class BuckGNN(nn.Module):
                                  skip, p, self.training, self._seed(), x_amax=amax, return_amax=True,
                                  amax_buf=bufs[i], w_in=None if fold is None else fold.weight,
                                  b_in=None if fold is None else fold.bias, wprep=wprep[i], count_batch=False,
-                                 fold_amax=fold_amax, rng=rng, pool=pl)
+                                 fold_amax=fold_amax, rng=rng, pool=pl, need_x=pl is None)
                 x, amax = out[0], out[1]
                 x_full = rng.holder[0] if (rng is not None and rng.holder) else None
             if pool is not None:

@@ -640,13 +640,18 @@ class LayerConfig:
         self.rng = None     # RangeRows (range rows of a stiffened batch) or None
 
 
+_E_ARG = 1001   # BGNN_E_ARG (include/bgnn.h)
+
+
 def _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean, running_var, cfg: LayerConfig, next_amax,
-              graph: Graph = None):
+              graph: Graph = None, pool=None, need_x: bool = True):
     """The layer glue after the normalised SAGE output o (Models/BuckGNN.py:436-444): BatchNorm
     finalize (train: batch statistics from the aggregation's partial sums, running stats updated;
     eval: running stats), then x_next = drop(relu(o * scale + shift) + skip * x_prev) with
-    max|x_next| folded into next_amax. Returns (x_next, (scale, shift, mean, invstd)) (None
-    coefficients without BN).
+    max|x_next| folded into next_amax. Returns (x_next, (scale, shift, mean, invstd), pooled) (None
+    coefficients without BN). pool (a SegmentIndex): the mean pool of x_next per segment comes out of
+    the same pass (pooled; None when the layer took the plain apply, and the caller pools x_next),
+    and with need_x False x_next is then neither written nor returned (None).
 
     The BatchNorm partials here are the UNSHIFTED f32 per-block sums of o and o^2 from the
     aggregation epilogue, reduced in fp64 (the per-module BatchNorm1d shifts by the first row,
@@ -687,11 +692,27 @@ def _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean, running_var,
         _lib.call("bgnn_range_sums_finish", rp.data_ptr(), N, H, graph.fwd.ref(), 0, full[N:].data_ptr(), H,
                   next_amax.data_ptr(), rng.out_amax.data_ptr(), s)
         rng.holder.append(full)
-        return x_next, (scale, shift, mean, invstd)
+        return x_next, (scale, shift, mean, invstd), None
+    if pool is not None and N > 0 and pool.n == N:
+        # the segment pool of x_next summed by the apply pass itself (bgnn_sage_apply_pool): x_next
+        # is not read back, and not written at all when nothing else reads it (need_x False)
+        x_next = torch.empty(N, H, dtype=torch.float32, device=dev) if need_x else None
+        pooled = torch.empty(pool.num_rows, H, dtype=torch.float32, device=dev)
+        nch = pool.fwd.plan.n_chunks
+        part = torch.empty(nch * H, dtype=torch.float32, device=dev) if nch else None
+        try:
+            _lib.call("bgnn_sage_apply_pool", o.data_ptr(), _ptr(scale), _ptr(shift), x_prev.data_ptr(),
+                      int(cfg.skip), float(cfg.p), cfg.seed, N, H, _ptr(x_next),
+                      next_amax.data_ptr() if need_x else None,   # (the scale of a GEMM that reads x_next)
+                      pool.fwd.ref(), 1, _ptr(part), pooled.data_ptr(), s)
+            return x_next, (scale, shift, mean, invstd), pooled
+        except _lib.BgnnError as e:
+            if e.code != _E_ARG:   # an unsupported shape takes the two-kernel path below
+                raise
     x_next = torch.empty(N, H, dtype=torch.float32, device=dev)
     _lib.call("bgnn_sage_apply", o.data_ptr(), _ptr(scale), _ptr(shift), x_prev.data_ptr(), int(cfg.skip),
               float(cfg.p), cfg.seed, N, H, x_next.data_ptr(), next_amax.data_ptr(), None, None, s)
-    return x_next, (scale, shift, mean, invstd)
+    return x_next, (scale, shift, mean, invstd), None
 
 
 def _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg: LayerConfig, g_rows=None):
@@ -736,7 +757,7 @@ class SageLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_prev, x_amax, w_l, b_l, w_r, gamma, beta, running_mean, running_var, graph: Graph,
-                cfg: LayerConfig, amax=None, w_in=None, b_in=None, wprep=None, pool=None):
+                cfg: LayerConfig, amax=None, w_in=None, b_in=None, wprep=None, pool=None, need_x: bool = True):
         dev = x_prev.device
         x_prev = x_prev.contiguous()
         H = w_l.size(0)
@@ -837,8 +858,8 @@ class SageLayerFn(torch.autograd.Function):
                       cfg.reduce, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), _ptr(part), _ptr(hagg),
                       2 * H if hagg is not None else 0, s)
         del z, zl, zr, hagg
-        x_next, (scale, shift, mean, invstd) = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
-                                                         running_var, cfg, next_amax, graph)
+        x_next, (scale, shift, mean, invstd), pooled = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
+                                                                 running_var, cfg, next_amax, graph, pool, need_x)
         ctx.graph = graph
         ctx.cfg = cfg
         ctx.folded = folded
@@ -855,9 +876,10 @@ class SageLayerFn(torch.autograd.Function):
         ctx.mark_non_differentiable(next_amax)
         ctx.pool = pool
         if pool is not None:
-            from .ops import spmm_fwd
-            pooled, _ = spmm_fwd(pool.fwd, x_next, 1, pool.num_rows)
-            return x_next, next_amax, pooled
+            if pooled is None:   # (the plain apply ran: range sums on this layer, or an unsupported shape)
+                from .ops import spmm_fwd
+                pooled, _ = spmm_fwd(pool.fwd, x_next, 1, pool.num_rows)
+            return (x_next if need_x else None), next_amax, pooled
         return x_next, next_amax
 
     @staticmethod
@@ -866,14 +888,18 @@ class SageLayerFn(torch.autograd.Function):
         g_rows = None
         if g_pool is not None:   # mean pool: segment gradient / count (bgnn.ops._SegmentReduce.backward)
             seg = ctx.pool
-            gp = g_pool.contiguous() / seg.fwd.degree().clamp_min(1).to(g_pool.dtype).unsqueeze(1)
+            # one launch with the bits of g_pool / seg.fwd.degree().clamp_min(1).to(float32).unsqueeze(1)
+            gpc = g_pool.contiguous()
+            gp = torch.empty_like(gpc)
+            _lib.call("bgnn_pool_grad_scale", gpc.data_ptr(), seg.fwd.rowptr.data_ptr(), gpc.size(0), gpc.size(1),
+                      gp.data_ptr(), _stream())
             if g is None and not cfg.skip:
                 g, g_rows = gp, seg.index
             else:
                 gb = gp.index_select(0, seg.index)
                 g = gb if g is None else g + gb
         if g is None:   # (materialize_grads off: the layer output did not reach the loss)
-            return (None,) * 16
+            return (None,) * 17
         x_prev, o, nrm, wcat, gamma, scale, shift, mean, invstd, x_amax, w_amax, dz_amax = ctx.saved_tensors
         graph: Graph = ctx.graph
         g = g.contiguous()
@@ -964,7 +990,7 @@ class SageLayerFn(torch.autograd.Function):
                 db_in = gemm(wcat, dbf.view(-1, 1), trans_a=True, trans_b=False, a_amax=fa[0],
                              b_amax=fa[4]).view(-1)                                        # [H]
             return (dx, None, dw[:H], db, dw[H:], dgamma if has_affine else None, dbeta if has_affine else None,
-                    None, None, None, None, None, dw_in, db_in, None, None)
+                    None, None, None, None, None, dw_in, db_in, None, None, None)
         # dx = dz · Wcat (+ skip gradient);  dWcat = dz^T · x_prev
         # [W_l;W_r] transposed once (2 MB) so the dgrad reads its B operand K-contiguous
         wcat_t = (ctx.wcat_t if ctx.wcat_t is not None else wcat.t().contiguous()) if DGRAD_WT else wcat
@@ -997,7 +1023,7 @@ class SageLayerFn(torch.autograd.Function):
             dw = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax)  # [2H, H]
         dw_l, dw_r = dw[:H], dw[H:]
         return (dx, None, dw_l, db, dw_r, dgamma if has_affine else None, dbeta if has_affine else None,
-                None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None)
 
 
 def _max_transform(x, w_l, w_r, graph: Graph, x_amax, w_amax, name: str):
@@ -1144,8 +1170,8 @@ class SageMaxLayerFn(torch.autograd.Function):
         with _timed("sage_fwd"):
             o, nrm, bn_part, slots = _max_rows_fwd(y, b_l, H)
         del y
-        x_next, (scale, shift, mean, invstd) = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
-                                                         running_var, cfg, next_amax)
+        x_next, (scale, shift, mean, invstd), _ = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
+                                                            running_var, cfg, next_amax)
         ctx.graph = graph
         ctx.cfg = cfg
         ctx.set_materialize_grads(False)
@@ -1296,7 +1322,7 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
                bn_module, graph: Graph, reduce: int, skip: bool, p: float, training: bool,
                seed: int, x_amax: torch.Tensor = None, return_amax: bool = False, amax_buf=None,
                w_in: torch.Tensor = None, b_in: torch.Tensor = None, wprep=None, count_batch: bool = True,
-               fold_amax: torch.Tensor = None, rng: RangeRows = None, pool=None):
+               fold_amax: torch.Tensor = None, rng: RangeRows = None, pool=None, need_x: bool = True):
     """Run one fused layer. `bn_module` is a torch.nn.BatchNorm1d (or None for no BN).
     x_amax: optional device scalar >= max|x_prev| (the previous layer's second output), which
     spares the GEMM a pass over x_prev; return_amax: also return max|x_next|.
@@ -1305,7 +1331,9 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
     without skip connection (the reference's first SAGE layer after the node encoder).
     rng: the range-row plumbing of a stiffened batch (RangeRows; sum / mean only).
     pool: a SegmentIndex (sum / mean only): also return the mean pool of x_next per segment as the
-    last element (SageLayerFn)."""
+    last element (SageLayerFn). need_x=False (with pool): the caller reads only the pool, so x_next
+    is returned as None and, where the pooling apply pass runs, never written (nor is max|x_next|
+    folded into the amax output then: it scales a GEMM that would read x_next)."""
     require_cuda(x_prev, w_l, b_l, w_r, what="sage_layer")
     _require_f32(x_prev, "sage_layer")
     H = w_l.size(0)
@@ -1339,7 +1367,7 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
         else:
             out = SageLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, bn_module.weight, bn_module.bias,
                                     bn_module.running_mean, bn_module.running_var, graph, cfg, amax_buf, w_in, b_in,
-                                    wprep, pool)
+                                    wprep, pool, need_x)
     else:
         cfg = LayerConfig(reduce, False, training, 0.0, 0.0, skip, p, seed)
         cfg.famax = fold_amax if w_in is not None else None
@@ -1349,7 +1377,7 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
                                        wprep)
         else:
             out = SageLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, None, None, None, None, graph, cfg, amax_buf,
-                                    w_in, b_in, wprep, pool)
+                                    w_in, b_in, wprep, pool, need_x)
     if pool is not None:
         return out if return_amax else (out[0], out[2])
     return out if return_amax else out[0]

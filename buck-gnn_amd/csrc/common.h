@@ -95,6 +95,9 @@ void set_rows_nt(int on);
 int rows_nt();
 void set_rows_rev(int on);
 int rows_rev();
+// bgnn_spmm_fwd's combine of the heavy rows' chunk partials [n_chunks, H] into out [n_rows, H]
+// (SUM / MEAN, float4 geometry: H % 4 == 0, 16-B aligned partial / out), launched alone (spmm.hip)
+int seg_combine_plain(const bgnn_csr_t* csr, int32_t H, int32_t reduce, float* partial, float* out, hipStream_t s);
 
 // 16-byte store, non-temporal (streamed once: no write-allocate in L2 / Infinity Cache)
 __device__ __forceinline__ void store4(float* p, float a, float b, float c, float d, bool nt) {

@@ -8,6 +8,7 @@
 // do not depend on scheduling.
 #include "common.h"
 #include "ranges.h"
+#include "seg_common.h"
 
 namespace bgnn {
 
@@ -217,6 +218,28 @@ __device__ __forceinline__ void block_amax(uint32_t* amax, uint32_t m) {
     }
 }
 
+// The element expression of x_next for one float4: y = o on entry, x_next on return;
+// drop(relu(o*scale+shift) + skip*x_prev), i = the float4's index row * H/4 + c4 (the dropout hash's
+// counter). One function for k_sage_apply, k_sage_apply_rows and k_sage_apply_pool: this file is
+// compiled with the default contraction (o*scale+shift is an FMA), and all three must round alike.
+__device__ __forceinline__ void x_next4(float (&y)[4], bool bn, const float4& sc, const float4& sh, bool skip,
+                                        const float4& p, uint32_t thr, float inv_keep, uint64_t seed, uint64_t i) {
+    if (bn) {
+        y[0] = y[0] * sc.x + sh.x; y[1] = y[1] * sc.y + sh.y;
+        y[2] = y[2] * sc.z + sh.z; y[3] = y[3] * sc.w + sh.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = fmaxf(y[k], 0.f);
+    if (skip) {
+        y[0] += p.x; y[1] += p.y; y[2] += p.z; y[3] += p.w;
+    }
+    if (thr) {
+        const uint32_t keep = keep_bits4(seed, i, thr);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = ((keep >> k) & 1u) ? y[k] * inv_keep : 0.f;
+    }
+}
+
 // x_next = drop(relu(o*scale+shift) + skip*x_prev). Grid-stride over float4s.
 __global__ __launch_bounds__(256) void k_sage_apply(const float4* __restrict__ o, const float* __restrict__ scale,
                                                     const float* __restrict__ shift,
@@ -242,23 +265,14 @@ __global__ __launch_bounds__(256) void k_sage_apply(const float4* __restrict__ o
         const int c = (int)(i % H4) * 4;
         float4 v = o[i];
         float y[4] = {v.x, v.y, v.z, v.w};
+        float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
         if (scale) {
-            const float4 sc = *reinterpret_cast<const float4*>(scale + c);
-            const float4 sh = *reinterpret_cast<const float4*>(shift + c);
-            y[0] = y[0] * sc.x + sh.x; y[1] = y[1] * sc.y + sh.y;
-            y[2] = y[2] * sc.z + sh.z; y[3] = y[3] * sc.w + sh.w;
+            sc = *reinterpret_cast<const float4*>(scale + c);
+            sh = *reinterpret_cast<const float4*>(shift + c);
         }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) y[k] = fmaxf(y[k], 0.f);
-        if (skip) {
-            const float4 p = xprev[i];
-            y[0] += p.x; y[1] += p.y; y[2] += p.z; y[3] += p.w;
-        }
-        if (thr) {
-            const uint32_t keep = keep_bits4(seed, (uint64_t)i, thr);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = ((keep >> k) & 1u) ? y[k] * inv_keep : 0.f;
-        }
+        if (skip) p = xprev[i];
+        x_next4(y, scale != nullptr, sc, sh, skip != 0, p, thr, inv_keep, seed, (uint64_t)i);
         store4(reinterpret_cast<float*>(xn + i), y[0], y[1], y[2], y[3], nt);
 #pragma unroll
         for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
@@ -316,21 +330,9 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
             const int64_t i = r * H4 + c4[v];
             const float4 ov = reinterpret_cast<const float4*>(o)[i];
             float y[4] = {ov.x, ov.y, ov.z, ov.w};
-            if (scale) {
-                y[0] = y[0] * sc[v].x + sh[v].x; y[1] = y[1] * sc[v].y + sh[v].y;
-                y[2] = y[2] * sc[v].z + sh[v].z; y[3] = y[3] * sc[v].w + sh[v].w;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = fmaxf(y[k], 0.f);
-            if (skip) {
-                const float4 p = reinterpret_cast<const float4*>(xprev)[i];
-                y[0] += p.x; y[1] += p.y; y[2] += p.z; y[3] += p.w;
-            }
-            if (thr) {
-                const uint32_t keep = keep_bits4(seed, (uint64_t)i, thr);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) y[k] = ((keep >> k) & 1u) ? y[k] * inv_keep : 0.f;
-            }
+            float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (skip) p = reinterpret_cast<const float4*>(xprev)[i];
+            x_next4(y, scale != nullptr, sc[v], sh[v], skip != 0, p, thr, inv_keep, seed, (uint64_t)i);
             store4(xn + 4 * i, y[0], y[1], y[2], y[3], nt);
 #pragma unroll
             for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
@@ -356,6 +358,136 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
         dst[c] = make_float4((a0.x + a1.x) + (a2.x + a3.x), (a0.y + a1.y) + (a2.y + a3.y),
                              (a0.z + a1.z) + (a2.z + a3.z), (a0.w + a1.w) + (a2.w + a3.w));
     }
+}
+
+// ---------------------------------------------------------------------------
+// k_sage_apply with the segment pool of x_next (bgnn_sage_apply_pool): the gather of spmm.hip's
+// k_seg_chunk / k_seg_light over the pooling CSR, whose "source row" col[e] is formed from o on the
+// fly (x_next4) instead of being read from a stored x_next. A wave owns one work item and one
+// column tile of 64 float4s; the `ct` tiles of an item (2 at H = 512) sit in one block, so a block
+// holds 4 / ct items. (Measured on the cfg2 pool, 1,264 chunks of 64 rows, H = 512: 41.7 us per
+// launch without amax against the 69 + 33 + 5 us of k_sage_apply, k_seg_chunk and the empty
+// light-row sweep it replaces. max |x_next| goes through block_amax, one atomic per block: with one
+// per wave, 2,528 atomics on one address, the launch took 58 us whatever the load schedule -- a
+// whole row per wave, or the next batch's loads issued ahead, measured the same -- and 17 us less
+// without them; the dropout hash costs 5 us of the rest.)
+// Items [0, n_chunks) are the chunks of the heavy segments (-> partial[c, :], finished by
+// k_seg_combine), items [n_chunks, n_chunks + n_light) the segments themselves, of which the light
+// ones (deg <= chunk) are finished here: sum, then * inv_deg for MEAN, as spmm.hip's store_plain.
+// The rows of a range are loaded 8 at a time (gather_range's batching: a load schedule only) and
+// added one by one in CSR order with a rounded add (__fadd_rn: no contraction with the dropout
+// scale), so the sums have the bits of bgnn_spmm_fwd over the stored rows. x_next (optional) is
+// stored on the way: every row lies in exactly one segment.
+struct ApplyPoolArgs {
+    const float* o;
+    const float* scale;
+    const float* shift;
+    const float* xprev;
+    uint32_t thr;
+    float inv_keep;
+    uint64_t seed;
+    int32_t H, nt;
+    float* xn;
+    uint32_t* amax;
+    const int32_t* rowptr;
+    const int32_t* col;
+    const int32_t* heavy_row;
+    const int32_t* heavy_chunk0;
+    const int32_t* chunk_heavy;
+    int32_t n_chunks, chunk, mean;
+    int32_t ct;        // column tiles per block (1, 2 or 4)
+    int64_t n_light;   // segments swept for light rows: n_seg, or 0 when every segment is heavy
+    float* partial;    // [n_chunks, H]
+    float* out;        // [n_seg, H]
+};
+
+// One batch of the gather: up to 8 rows of the range in flight (slots >= nvalid re-read the first
+// row and are not added or stored), then x_next of each row and the adds, in order.
+template <bool SKIP>
+__device__ __forceinline__ void apply_pool_batch(const ApplyPoolArgs& A, float (&acc)[4], uint32_t& m, int32_t e,
+                                                 int32_t nvalid, int c4, bool cok, const float4& sc,
+                                                 const float4& sh) {
+    constexpr int U = 8;
+    const int H4 = A.H / 4;
+    int64_t i[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) i[u] = (int64_t)A.col[e + (u < nvalid ? u : 0)] * H4 + c4;
+    float4 ov[U], pv[SKIP ? U : 1];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        ov[u] = reinterpret_cast<const float4*>(A.o)[i[u]];
+        if constexpr (SKIP) pv[u] = reinterpret_cast<const float4*>(A.xprev)[i[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const bool ok = cok && u < nvalid;
+        float y[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w};
+        x_next4(y, A.scale != nullptr, sc, sh, SKIP, SKIP ? pv[u] : make_float4(0.f, 0.f, 0.f, 0.f), A.thr,
+                A.inv_keep, A.seed, (uint64_t)i[u]);
+        if (ok) {
+            if (A.xn) store4(A.xn + 4 * i[u], y[0], y[1], y[2], y[3], A.nt);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], ok ? y[k] : 0.f);
+    }
+}
+
+template <bool SKIP>
+__global__ __launch_bounds__(256) void k_sage_apply_pool(ApplyPoolArgs A) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int H4 = A.H / 4;
+    const int tile = blockIdx.y * A.ct + wave % A.ct;
+    const int64_t w = (int64_t)blockIdx.x * (4 / A.ct) + wave / A.ct;
+    // (a wave without work -- a tile past the row, an item past the last, a heavy segment's own item
+    // -- keeps an empty range and stays for block_amax's barrier)
+    bool live = tile * 64 < H4;   // (wave-uniform)
+    int32_t beg = 0, end = 0;
+    int64_t seg = -1;
+    if (live && w < A.n_chunks) {
+        const int32_t h = A.chunk_heavy[w];
+        const int32_t r = A.heavy_row[h];
+        const int32_t k = (int32_t)(w - A.heavy_chunk0[h]);
+        beg = A.rowptr[r] + k * A.chunk;
+        end = min(beg + A.chunk, A.rowptr[r + 1]);
+    } else if (live) {
+        seg = w - A.n_chunks;
+        live = seg < A.n_light;
+        if (live) {
+            beg = A.rowptr[seg];
+            end = A.rowptr[seg + 1];
+            if (end - beg > A.chunk) {   // heavy segment: its chunks above + k_seg_combine
+                live = false;
+                end = beg;
+            }
+        }
+    }
+    const bool cok = tile * 64 + lane < H4;
+    const int c4 = cok ? tile * 64 + lane : 0;   // (lanes past the row read column 0 and keep nothing)
+    const float4 sc = A.scale ? *reinterpret_cast<const float4*>(A.scale + 4 * c4) : make_float4(1.f, 1.f, 1.f, 1.f);
+    const float4 sh = A.shift ? *reinterpret_cast<const float4*>(A.shift + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    uint32_t m = 0;
+    int32_t e = beg;
+    for (; e + 8 <= end; e += 8) apply_pool_batch<SKIP>(A, acc, m, e, 8, c4, cok, sc, sh);
+    if (e < end) apply_pool_batch<SKIP>(A, acc, m, e, end - e, c4, cok, sc, sh);
+    if (A.amax) block_amax(A.amax, m);   // one atomic per block: same-address atomics serialise in L2
+    if (!live || !cok) return;
+    const float s = (seg >= 0 && A.mean) ? inv_deg(end - beg) : 1.f;
+    float* dst = seg >= 0 ? A.out + seg * A.H : A.partial + w * A.H;
+    *reinterpret_cast<float4*>(dst + 4 * c4) = make_float4(acc[0] * s, acc[1] * s, acc[2] * s, acc[3] * s);
+}
+
+// gp = g / max(count, 1) per segment row (bgnn_pool_grad_scale): IEEE division
+__global__ __launch_bounds__(256) void k_pool_grad_scale(const float* __restrict__ g, const int32_t* __restrict__ rowptr,
+                                                         int64_t n, int H, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t s = i / H;
+    const int32_t d = rowptr[s + 1] - rowptr[s];
+    out[i] = __fdiv_rn(g[i], (float)(d > 0 ? d : 1));
 }
 
 // Backward pass 1: partial sums over rows of g2 and g2*xhat per channel.
@@ -917,6 +1049,73 @@ extern "C" int bgnn_sage_apply(const float* o, const float* scale, const float* 
     hipLaunchKernelGGL(k_sage_apply, dim3((unsigned)blocks), dim3(256), 0, s, (const float4*)o, scale, shift,
                        (const float4*)x_prev, skip, thr, inv_keep, seed, n4, H / 4, (float4*)x_next,
                        reinterpret_cast<uint32_t*>(amax), rows_nt(), rev);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
+
+extern "C" int bgnn_sage_apply_pool(const float* o, const float* scale, const float* shift, const float* x_prev,
+                                    int32_t skip, float p, uint64_t seed, int64_t n_rows, int32_t H, float* x_next,
+                                    float* amax, const bgnn_csr_t* pool, int32_t reduce, float* partial,
+                                    float* pooled, void* stream) {
+    BGNN_REQUIRE(H > 0 && H % 4 == 0, "sage_apply_pool: H must be a multiple of 4");
+    BGNN_REQUIRE(n_rows >= 0, "sage_apply_pool: negative n_rows");
+    BGNN_REQUIRE(n_rows == 0 || o, "sage_apply_pool: null o");
+    BGNN_REQUIRE(p >= 0.f && p < 1.f, "sage_apply_pool: dropout p must be in [0, 1)");
+    BGNN_REQUIRE((scale == nullptr) == (shift == nullptr), "sage_apply_pool: scale/shift must both be set or NULL");
+    BGNN_REQUIRE(!skip || x_prev, "sage_apply_pool: skip requires x_prev");
+    BGNN_REQUIRE(al16(o) && al16(x_next) && (!x_prev || al16(x_prev)) && (!scale || (al16(scale) && al16(shift))),
+                 "sage_apply_pool: pointers must be 16-byte aligned");
+    BGNN_REQUIRE(pool && pool->rowptr, "sage_apply_pool: null pool csr");
+    BGNN_REQUIRE(reduce == BGNN_REDUCE_SUM || reduce == BGNN_REDUCE_MEAN, "sage_apply_pool: reduce must be sum/mean");
+    BGNN_REQUIRE(pool->n_rows >= 0, "sage_apply_pool: negative segment count");
+    BGNN_REQUIRE(pool->nnz == n_rows, "sage_apply_pool: the pool must list each of the n_rows rows once (nnz = %lld)",
+                 (long long)pool->nnz);
+    BGNN_REQUIRE(n_rows == 0 || pool->col, "sage_apply_pool: null col");
+    BGNN_REQUIRE(pool->n_rows == 0 || pooled, "sage_apply_pool: null pooled");
+    BGNN_REQUIRE(pool->n_chunks <= 0 ||
+                     (partial && pool->chunk > 0 && pool->heavy_row && pool->heavy_chunk0 && pool->chunk_heavy),
+                 "sage_apply_pool: heavy segments need partial and the CSR's chunk plan");
+    BGNN_REQUIRE(al16(partial) && al16(pooled), "sage_apply_pool: partial / pooled must be 16-byte aligned");
+    if (n_rows == 0) return BGNN_OK;
+    hipStream_t s = as_stream(stream);
+    ApplyPoolArgs A{};
+    A.o = o; A.scale = scale; A.shift = shift; A.xprev = x_prev;
+    A.thr = dropout_threshold(p);
+    A.inv_keep = A.thr ? 1.f / (1.f - p) : 1.f;
+    A.seed = seed;
+    A.H = H;
+    A.nt = rows_nt();
+    A.xn = x_next;
+    A.amax = reinterpret_cast<uint32_t*>(amax);
+    A.rowptr = pool->rowptr; A.col = pool->col;
+    A.heavy_row = pool->heavy_row; A.heavy_chunk0 = pool->heavy_chunk0; A.chunk_heavy = pool->chunk_heavy;
+    A.n_chunks = pool->n_chunks > 0 ? pool->n_chunks : 0;
+    A.chunk = (A.n_chunks > 0 && pool->chunk > 0) ? pool->chunk : 0x7fffffff;   // no chunk plan: every segment light
+    A.mean = reduce == BGNN_REDUCE_MEAN;
+    // no light-row items when the plan says every segment is heavy (a batch of large graphs)
+    A.n_light = (A.n_chunks > 0 && pool->n_heavy == pool->n_rows) ? 0 : pool->n_rows;
+    A.partial = partial;
+    A.out = pooled;
+    const int64_t items = A.n_chunks + A.n_light;
+    const int tiles = (H / 4 + 63) / 64;
+    A.ct = tiles <= 2 ? tiles : 4;   // (a divisor of the block's 4 waves; a tile past the row leaves at once)
+    const int ipb = 4 / A.ct;        // items per block
+    const dim3 grid((unsigned)((items + ipb - 1) / ipb), (unsigned)((tiles + A.ct - 1) / A.ct));
+    if (skip) hipLaunchKernelGGL(k_sage_apply_pool<true>, grid, dim3(256), 0, s, A);
+    else hipLaunchKernelGGL(k_sage_apply_pool<false>, grid, dim3(256), 0, s, A);
+    BGNN_CHECK_LAUNCH();
+    if (A.n_chunks > 0) return seg_combine_plain(pool, H, reduce, partial, pooled, s);
+    return BGNN_OK;
+}
+
+extern "C" int bgnn_pool_grad_scale(const float* g, const int32_t* rowptr, int64_t segments, int32_t H, float* out,
+                                    void* stream) {
+    BGNN_REQUIRE(segments >= 0 && H > 0, "pool_grad_scale: bad sizes");
+    BGNN_REQUIRE(segments == 0 || (g && rowptr && out), "pool_grad_scale: null pointer");
+    if (segments == 0) return BGNN_OK;
+    const int64_t n = segments * H;
+    hipLaunchKernelGGL(k_pool_grad_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), g, rowptr,
+                       n, H, out);
     BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }

@@ -1200,6 +1200,24 @@ inline int check_plain(const char* name, const char* xn, const char* on, const b
     return BGNN_OK;
 }
 
+// The heavy rows' combine on its own, for a caller that wrote the chunk partials itself
+// (bgnn_sage_apply_pool, sage.hip): the launch of launch_all<4, 2, 64, SUM / MEAN, EPI_PLAIN>. A
+// column's run tree does not depend on the lane that holds it, so every H takes this one geometry.
+int seg_combine_plain(const bgnn_csr_t* csr, int32_t H, int32_t reduce, float* partial, float* out, hipStream_t s) {
+    SegArgs A = args_from_csr(csr);
+    A.H = H;
+    A.out = out; A.ldo = H;
+    A.partial = partial;
+    A.nt = g_seg_nt;
+    const dim3 grid(A.n_heavy, (H + 511) / 512);
+    if (reduce == BGNN_REDUCE_MEAN)
+        hipLaunchKernelGGL((k_seg_combine<4, 2, 64, OP_MEAN, EPI_PLAIN>), grid, dim3(64 * kCombineWaves), 0, s, A);
+    else
+        hipLaunchKernelGGL((k_seg_combine<4, 2, 64, OP_SUM, EPI_PLAIN>), grid, dim3(64 * kCombineWaves), 0, s, A);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
+
 extern int g_x6_bdma;   // gemm_x6.hip
 extern int g_h3p_nsb;   // gemm_h3p.hip
 #ifdef BGNN_H3P_ABLATION

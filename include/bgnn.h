@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 17
+#define BGNN_ABI_VERSION 18
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -336,6 +336,37 @@ int bgnn_sage_apply(const float* o, const float* scale, const float* shift,
  * H % 4 != 0 (ranges: H > 512); p outside [0, 1); exactly one of scale / shift is NULL; skip
  * without x_prev; ranges without range_partial; a pointer is not 16-byte aligned. n_rows == 0
  * returns BGNN_OK without a launch. */
+
+/* bgnn_sage_apply with the segment pool of x_next in the same pass (ABI 18; the last SAGE layer of
+ * the buckling model, whose x_next only feeds global_mean_pool, Models/BuckGNN.py:246-249):
+ *   pooled[s, :] = REDUCE_{e in segment s} x_next[col[e], :]        (SUM or MEAN)
+ * with x_next[r] the row bgnn_sage_apply computes (the same expression, the dropout hash at the same
+ * element index), never read back from memory. `pool` is a CSR over segments whose col lists every
+ * row of [0, n_rows) exactly once (bgnn_index_csr_build of a batch vector: nnz == n_rows). The rows
+ * of a segment are added in CSR order into an accumulator that starts at 0; segments with more
+ * than `chunk` rows go by chunks into `partial` ([n_chunks, H]) and are combined by bgnn_spmm_fwd's
+ * combine kernel, so pooled has the bits of bgnn_sage_apply followed by bgnn_spmm_fwd(pool, x_next).
+ * Empty segments give 0. x_next (optional): the rows are also stored, and max |x_next| is folded
+ * into amax (optional) either way; with x_next == NULL nothing of size [n_rows, H] is written.
+ * pooled is [pool->n_rows, H], contiguous.
+ * BGNN_E_ARG, before anything is launched, when: bgnn_sage_apply's conditions on H, n_rows, o, p,
+ * scale / shift, skip and alignment (x_next may be NULL); pool or its rowptr is NULL; reduce is not
+ * SUM / MEAN; pool->n_rows < 0; pool->nnz != n_rows; col is NULL; pooled is NULL with segments;
+ * the CSR has chunks and partial or a pointer of the chunk plan is NULL, or chunk <= 0; partial or
+ * pooled is not 16-byte aligned. n_rows == 0 returns BGNN_OK without a launch (pooled not written). */
+int bgnn_sage_apply_pool(const float* o, const float* scale, const float* shift,
+                         const float* x_prev, int32_t skip, float p, uint64_t seed,
+                         int64_t n_rows, int32_t H, float* x_next, float* amax,
+                         const bgnn_csr_t* pool, int32_t reduce, float* partial, float* pooled,
+                         void* stream);
+
+/* The gradient of a mean pool per segment (ABI 18): out[s, c] = g[s, c] / max(count_s, 1) with
+ * count_s = rowptr[s + 1] - rowptr[s], an IEEE division (the bits of torch's
+ * g / count.clamp_min(1).to(float32).unsqueeze(1)). g and out are [segments, H], contiguous; out
+ * may alias g. BGNN_E_ARG, before anything is launched, when: segments < 0 or H <= 0; g, rowptr or
+ * out is NULL with segments > 0. segments == 0 returns BGNN_OK without a launch. */
+int bgnn_pool_grad_scale(const float* g, const int32_t* rowptr, int64_t segments, int32_t H,
+                         float* out, void* stream);
 
 /* Eval-mode SAGE layer on bf16 rows (ABI 14): the aggregation of bgnn_sage_fwd and the tail of
  * bgnn_sage_apply (no dropout) in one pass over z = x [W_l ; W_r]^T stored as bf16 [N, 2H]
