@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BGNN_LIBRARY: a measurement build of the same ABI (make -C buck-gnn_amd m16), for tools/ only
 LIB_PATH = os.environ.get("BGNN_LIBRARY") or os.path.join(_HERE, "_lib", "libbgnn.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _lock = threading.Lock()
 _lib = None
@@ -107,6 +107,8 @@ SIGNATURES = {
     "bgnn_pool_grad_scale": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_p]),
     "bgnn_sage_infer_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i32, c_i32,
                                      c_p, c_i64, c_i32, c_p, c_p]),
+    "bgnn_sage_fwd_bf16_slots": (c_i32, [ctypes.POINTER(CsrStruct)]),
+    "bgnn_sage_fwd_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_i64, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
     "bgnn_spmm_fwd_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_i64, c_i32, c_i32, c_p, c_i64, c_i32, c_p, c_p]),
     "bgnn_spmm_bwd_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_p, c_i64, c_i32, c_i32, c_p, c_i64, c_i32, c_p,
                                    c_p]),

@@ -41,6 +41,9 @@ FOLD_ENCODER = True
 # per-graph mean pool (fused.SageLayerFn pool), so its backward reads the pooled gradient through
 # the batch vector instead of an [N, H] broadcast (A/B switch; the same bits)
 FUSED_POOL = True
+# default of BuckGNN.sage_bf16 for models built afterwards: the fused sum / mean SAGE layer loop
+# with autocast's rounding points (BuckGNN._sage_bf16_on)
+SAGE_BF16 = False
 
 _SAGE_VARIANTS = {
     # model_name: (ModuleList attribute, aggr, has BatchNorm)
@@ -206,6 +209,14 @@ class BuckGNN(nn.Module):
         # "all": as True, and GraphSage_maxAggr too, on bf16 rows with a gather, a K = 2H GEMM and a
         # tail kernel per layer (fused.sage_infer_max_layer); under True a max model stays f32.
         self.infer_bf16 = False
+        # GraphSAGE sum / mean models (and GraphSage_addAggr_Shared) on the fused layer loop, training
+        # included: the operands of every N-row Linear product rounded to bf16 and z = x [W_l;W_r]^T
+        # stored as bf16, as torch.autocast(bf16) would; accumulators, normalize, BatchNorm, skip,
+        # dropout, the stored activations, all gradients and the decoder stay f32
+        # (fused.sage_layer bf16=True). Off: the f32-accurate path. A shape outside the mode takes the
+        # f32 path silently; infer_bf16 keeps precedence where it applies. (_sage_bf16_on)
+        # The encoder then runs whole and in f32 (no fold into layer 0).
+        self.sage_bf16 = SAGE_BF16
         self._step = 0
 
     # ------------------------------------------------------------------ pooling
@@ -275,6 +286,13 @@ class BuckGNN(nn.Module):
                     and (bns is None or all(bn.track_running_stats and bn.running_mean is not None
                                             for bn in bns)))
 
+    def _sage_bf16_on(self, x: Tensor, aggr: str) -> bool:
+        """Whether the fused SAGE layer loop runs with autocast's rounding points (sage_bf16): the
+        fused path on f32 input, a sum / mean aggregation and rows of whole 16-byte bf16 vectors."""
+        h = self.hidden_channels
+        return bool(self.sage_bf16 and self._sage_fused(x, aggr) and aggr in ("add", "sum", "mean")
+                    and h % 8 == 0 and h <= 512)
+
     def _sage_loop_bf16(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, pool=None):
         """The eval-mode SAGE layer loop on bf16 rows: per layer one bf16 GEMM and one aggregation +
         tail kernel; the last layer writes f32 for the pooling and the decoder."""
@@ -343,11 +361,14 @@ class BuckGNN(nn.Module):
             scratch = torch.zeros(4 * L + 5, dtype=torch.float32, device=x.device)
             bufs, fold_amax = scratch[:4 * L].view(L, 4), scratch[4 * L:]
             layers = [convs[i] if convs is not None else self.shared_graphsage_block for i in range(L)]
-            rng_on = _range_rows_on(graph, red, x.size(0), layers[0].lin_l.weight.size(0))
+            # sage_bf16: no range rows (heavy rows by chunk + combine), and of the prepared weights only
+            # the packed [W_l;W_r] and its transpose (no operand maxima, no pre-split images)
+            b16 = self._sage_bf16_on(x, aggr)
+            rng_on = not b16 and _range_rows_on(graph, red, x.size(0), layers[0].lin_l.weight.size(0))
             R = graph.fwd.plan.n_heavy if rng_on else 0
             wprep = prepare_weights([(c.lin_l.weight, c.lin_r.weight) for c in layers], bufs,
-                                    [not (i == 0 and x_in is not None) for i in range(L)],
-                                    n_rows=x.size(0) + R if red != 2 else 0)
+                                    [not b16 and not (i == 0 and x_in is not None) for i in range(L)],
+                                    n_rows=x.size(0) + R if (red != 2 and not b16) else 0)
             self._count_bn_batches(bns)
             x_full = None
             for i in range(L):
@@ -362,7 +383,7 @@ class BuckGNN(nn.Module):
                                  skip, p, self.training, self._seed(), x_amax=amax, return_amax=True,
                                  amax_buf=bufs[i], w_in=None if fold is None else fold.weight,
                                  b_in=None if fold is None else fold.bias, wprep=wprep[i], count_batch=False,
-                                 fold_amax=fold_amax, rng=rng, pool=pl, need_x=pl is None)
+                                 fold_amax=fold_amax, rng=rng, pool=pl, need_x=pl is None, bf16=b16)
                 x, amax = out[0], out[1]
                 x_full = rng.holder[0] if (rng is not None and rng.holder) else None
             if pool is not None:
@@ -445,9 +466,13 @@ class BuckGNN(nn.Module):
         # the bf16 inference loop takes the encoder's f32 output: the encoder stays unfolded
         infer = ((name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared")
                  and self._infer_bf16_on(x, sage, self.batch_norms if name in _SAGE_VARIANTS else None))
+        # sage_bf16 keeps the encoder f32 and whole: folded, its last Linear would join layer 0's bf16
+        # product (h and [W_l;W_r] W_in rounded instead of x0 and [W_l;W_r]: not autocast's points)
+        unfold = ((name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared")
+                  and self._sage_bf16_on(x, sage))
         # (GraphSAGE_SAG folds into sage_layers_1[0]: not when that list is empty, num_layers == 1)
         if (name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"
-                or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) and not infer \
+                or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) and not infer and not unfold \
                 and self._sage_fused(x, sage) and sage != "max" and self._foldable_encoder(x):
             x_in = self.node_encoder[-1]
             x, x_amax = mlp(self.node_encoder[:-1], x, return_amax=True)

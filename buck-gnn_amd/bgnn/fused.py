@@ -621,7 +621,7 @@ RANGE_ROWS = True
 
 
 class LayerConfig:
-    __slots__ = ("reduce", "bn", "training", "momentum", "eps", "skip", "p", "seed", "famax", "rng")
+    __slots__ = ("reduce", "bn", "training", "momentum", "eps", "skip", "p", "seed", "famax", "rng", "bf16")
 
     def __init__(self, reduce: int, bn: bool, training: bool, momentum: float, eps: float, skip: bool,
                  p: float, seed: int):
@@ -638,6 +638,9 @@ class LayerConfig:
         # max pass (and no zero fill) of their own
         self.famax = None
         self.rng = None     # RangeRows (range rows of a stiffened batch) or None
+        # sum / mean layer with autocast's rounding points (sage_layer bf16=True): bf16 operands in
+        # the N-row products, z stored bf16, everything else f32
+        self.bf16 = False
 
 
 _E_ARG = 1001   # BGNN_E_ARG (include/bgnn.h)
@@ -813,12 +816,12 @@ class SageLayerFn(torch.autograd.Function):
                 absmax(wf, w_amax, accumulate=True)
             wmat = wf
         else:
-            if wprep is None:
+            if wprep is None and not cfg.bf16:
                 absmax(wcat, w_amax, accumulate=True)
             wmat, bf = wcat, None
-        if x_amax is None:
-            x_amax = absmax(x_prev)
-        planes = Z_PLANES and H % PLANE_TILE == 0 and not folded
+        if x_amax is None:   # (the bf16 products take no operand scale: a placeholder for the saved list)
+            x_amax = torch.empty(0, dtype=torch.float32, device=dev) if cfg.bf16 else absmax(x_prev)
+        planes = Z_PLANES and H % PLANE_TILE == 0 and not folded and not cfg.bf16
         # range rows (RangeRows): x_prev is the head of an [N + R, H] buffer whose last R rows are the
         # range sums of x_prev; the GEMM runs on all N + R rows and z_l's extra rows are the range
         # rows' aggregates
@@ -831,7 +834,10 @@ class SageLayerFn(torch.autograd.Function):
         # (the folded layer's transform has K = K_in, not H: timed under its own name so the
         # bench's flops per launch are right for every launch it averages)
         with _timed("gemm_fwd_fold" if folded else "gemm_fwd"):
-            if planes:   # z = [z_l ; z_r] as two dense [N, H] planes
+            if cfg.bf16:   # operands rounded to bf16 in-tile, z [N, 2H] stored bf16 (bgnn_gemm_bf16 storage 4)
+                z = gemm_bf16(x_prev, wmat, trans_a=False, trans_b=True, out_bf16=True)
+                zl = zr = None
+            elif planes:   # z = [z_l ; z_r] as two dense [N, H] planes
                 z = torch.empty(2, N, H, dtype=torch.float32, device=dev)
                 gemm(x_prev, wmat, trans_a=False, trans_b=True, out=Planes(z), a_amax=x_amax, b_amax=w_amax)
                 zl, zr, ldz = z[0], z[1], H
@@ -848,15 +854,20 @@ class SageLayerFn(torch.autograd.Function):
         hagg = z[N:] if x_full is not None else None
         o = torch.empty(N, H, dtype=torch.float32, device=dev)
         nrm = torch.empty(N, dtype=torch.float32, device=dev)
-        slots = _lib.query("bgnn_sage_fwd_slots", graph.fwd.ref())
+        slots = _lib.query("bgnn_sage_fwd_bf16_slots" if cfg.bf16 else "bgnn_sage_fwd_slots", graph.fwd.ref())
         bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)
         part = (torch.empty(graph.fwd.plan.n_chunks * H, dtype=torch.float32, device=dev)
                 if graph.fwd.plan.n_chunks else None)
         s = _stream()
         with _timed("sage_fwd"):
-            _lib.call("bgnn_sage_fwd", graph.fwd.ref(), zl.data_ptr(), ldz, zr.data_ptr(), ldz, b_l.data_ptr(), H,
-                      cfg.reduce, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), _ptr(part), _ptr(hagg),
-                      2 * H if hagg is not None else 0, s)
+            if cfg.bf16:   # (batch statistics only where _glue_fwd reads them)
+                _lib.call("bgnn_sage_fwd_bf16", graph.fwd.ref(), z.data_ptr(), z.stride(0), b_l.data_ptr(), H,
+                          cfg.reduce, o.data_ptr(), nrm.data_ptr(),
+                          bn_part.data_ptr() if (cfg.bn and cfg.training) else None, _ptr(part), s)
+            else:
+                _lib.call("bgnn_sage_fwd", graph.fwd.ref(), zl.data_ptr(), ldz, zr.data_ptr(), ldz, b_l.data_ptr(), H,
+                          cfg.reduce, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), _ptr(part), _ptr(hagg),
+                          2 * H if hagg is not None else 0, s)
         del z, zl, zr, hagg
         x_next, (scale, shift, mean, invstd), pooled = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
                                                                  running_var, cfg, next_amax, graph, pool, need_x)
@@ -904,7 +915,8 @@ class SageLayerFn(torch.autograd.Function):
         graph: Graph = ctx.graph
         g = g.contiguous()
         N, H = o.shape
-        planes = DZ_PLANES and H % PLANE_TILE == 0
+        b16 = cfg.bf16   # the N-row dgrad / wgrad on bf16 operands; the row passes and A^T stay f32
+        planes = DZ_PLANES and H % PLANE_TILE == 0 and not b16
         dev = o.device
         s = _stream()
         bn = cfg.bn
@@ -917,7 +929,8 @@ class SageLayerFn(torch.autograd.Function):
             dzl, dh, lddz = dz, dz[:, H:], 2 * H
         # skip layers: the dgrad's epilogue adds drop(g) itself (bgnn_gemm_f32_dropadd), so
         # bgnn_sage_bwd_rows does not write the [N, H] skip gradient
-        dropadd = (cfg.skip and DGRAD_DROPADD and GEMM_BACKEND == "hip" and DGRAD_WT and not planes
+        # (the bf16 products have no drop-add epilogue: their skip gradient takes the gskip route)
+        dropadd = (cfg.skip and DGRAD_DROPADD and GEMM_BACKEND == "hip" and DGRAD_WT and not planes and not b16
                    and H % 4 == 0 and _lib.query("bgnn_get_tuning", 5) == 2)
         gskip = torch.empty(N, H, dtype=torch.float32, device=dev) if (cfg.skip and not dropadd) else None
         rs = _lib.query("bgnn_rows_slots", N)
@@ -994,7 +1007,7 @@ class SageLayerFn(torch.autograd.Function):
         # dx = dz · Wcat (+ skip gradient);  dWcat = dz^T · x_prev
         # [W_l;W_r] transposed once (2 MB) so the dgrad reads its B operand K-contiguous
         wcat_t = (ctx.wcat_t if ctx.wcat_t is not None else wcat.t().contiguous()) if DGRAD_WT else wcat
-        img_d = ctx.img_d if (not planes and DGRAD_WT) else None
+        img_d = ctx.img_d if (not planes and DGRAD_WT and not b16) else None
         if (img_d is not None and (dropadd or gskip is None)
                 and _lib.query("bgnn_gemm_w_tile", N, H, 2 * H) == img_d.bn_d):   # pre-split [W_l;W_r]^T
             dx = torch.empty(N, H, dtype=torch.float32, device=dev)
@@ -1015,12 +1028,12 @@ class SageLayerFn(torch.autograd.Function):
         elif gskip is not None:
             with _timed("gemm_dgrad"):
                 dx = gemm(dz, wcat_t, trans_a=False, trans_b=DGRAD_WT, out=gskip, beta=1.0, a_amax=dz_amax,
-                          b_amax=w_amax)
+                          b_amax=w_amax, bf16=b16)
         else:
             with _timed("gemm_dgrad"):
-                dx = gemm(dz, wcat_t, trans_a=False, trans_b=DGRAD_WT, a_amax=dz_amax, b_amax=w_amax)
+                dx = gemm(dz, wcat_t, trans_a=False, trans_b=DGRAD_WT, a_amax=dz_amax, b_amax=w_amax, bf16=b16)
         with _timed("gemm_wgrad"):
-            dw = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax)  # [2H, H]
+            dw = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax, bf16=b16)  # [2H, H]
         dw_l, dw_r = dw[:H], dw[H:]
         return (dx, None, dw_l, db, dw_r, dgamma if has_affine else None, dbeta if has_affine else None,
                 None, None, None, None, None, None, None, None, None, None)
@@ -1322,7 +1335,8 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
                bn_module, graph: Graph, reduce: int, skip: bool, p: float, training: bool,
                seed: int, x_amax: torch.Tensor = None, return_amax: bool = False, amax_buf=None,
                w_in: torch.Tensor = None, b_in: torch.Tensor = None, wprep=None, count_batch: bool = True,
-               fold_amax: torch.Tensor = None, rng: RangeRows = None, pool=None, need_x: bool = True):
+               fold_amax: torch.Tensor = None, rng: RangeRows = None, pool=None, need_x: bool = True,
+               bf16: bool = False):
     """Run one fused layer. `bn_module` is a torch.nn.BatchNorm1d (or None for no BN).
     x_amax: optional device scalar >= max|x_prev| (the previous layer's second output), which
     spares the GEMM a pass over x_prev; return_amax: also return max|x_next|.
@@ -1333,7 +1347,12 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
     pool: a SegmentIndex (sum / mean only): also return the mean pool of x_next per segment as the
     last element (SageLayerFn). need_x=False (with pool): the caller reads only the pool, so x_next
     is returned as None and, where the pooling apply pass runs, never written (nor is max|x_next|
-    folded into the amax output then: it scales a GEMM that would read x_next)."""
+    folded into the amax output then: it scales a GEMM that would read x_next).
+    bf16 (sum / mean, H % 8 == 0): autocast's rounding points -- the operands of the layer's N-row
+    products (transform, dgrad, wgrad) are rounded to bf16 and z = x [W_l;W_r]^T is stored as bf16
+    (bgnn_gemm_bf16, bgnn_sage_fwd_bf16); accumulators, bias, normalize, BatchNorm, ReLU, skip,
+    dropout, the stored x / o / dh and every gradient stay f32. Range rows, pre-split weight images
+    and the operand maxima are not used then (rng is ignored), and w_in / b_in are refused."""
     require_cuda(x_prev, w_l, b_l, w_r, what="sage_layer")
     _require_f32(x_prev, "sage_layer")
     H = w_l.size(0)
@@ -1347,6 +1366,11 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
         raise ValueError("sage_layer: max aggregation needs its input rows (no folded input transform)")
     if reduce == 2 and pool is not None:
         raise ValueError("sage_layer: the fused mean pool is for sum / mean layers")
+    if bf16 and (reduce == 2 or H % 8):
+        raise ValueError(f"sage_layer: bf16 needs a sum / mean layer with H % 8 == 0 (got reduce {reduce}, H {H})")
+    if bf16 and w_in is not None:
+        raise ValueError("sage_layer: bf16 takes no folded input transform (w_in): the folded Linear would join "
+                         "the layer's bf16 product")
     if bn_module is not None:
         use_batch_stats = training or not bn_module.track_running_stats
         momentum = bn_module.momentum
@@ -1360,7 +1384,8 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
                           else 0.0, float(bn_module.eps), skip, p, seed)
         cfg.p = p if training else 0.0
         cfg.famax = fold_amax if w_in is not None else None
-        cfg.rng = rng if reduce != 2 else None
+        cfg.rng = rng if (reduce != 2 and not bf16) else None
+        cfg.bf16 = bool(bf16)
         if reduce == 2:
             out = SageMaxLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, bn_module.weight, bn_module.bias,
                                        bn_module.running_mean, bn_module.running_var, graph, cfg, amax_buf, wprep)
@@ -1371,7 +1396,8 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
     else:
         cfg = LayerConfig(reduce, False, training, 0.0, 0.0, skip, p, seed)
         cfg.famax = fold_amax if w_in is not None else None
-        cfg.rng = rng if reduce != 2 else None
+        cfg.rng = rng if (reduce != 2 and not bf16) else None
+        cfg.bf16 = bool(bf16)
         if reduce == 2:
             out = SageMaxLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, None, None, None, None, graph, cfg, amax_buf,
                                        wprep)

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 18
+#define BGNN_ABI_VERSION 19
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -389,6 +389,33 @@ int bgnn_sage_infer_bf16(const bgnn_csr_t* csr, const void* z, int64_t ldz, cons
                          const float* scale, const float* shift, const void* x_prev, int64_t ldx,
                          int32_t H, int32_t reduce, void* out, int64_t ldo, int32_t out_f32,
                          float* partial, void* stream);
+
+/* Training-mode SAGE aggregation on bf16 rows (ABI 19): bgnn_sage_fwd's contract over
+ * z = x [W_l ; W_r]^T stored as bf16 [N, ldz] (z_l = columns [0, H), the gathered rows; z_r = columns
+ * [H, 2H), the row's own; bgnn_gemm_bf16 storage 4 or 7). Per row i, in f32:
+ *   h = s_i * sum_{e in row i} z_l[col[e]] + z_r[i] + bias     (s_i = 1, or 1 / max(deg, 1) for MEAN;
+ *                                                              empty rows aggregate to 0; bias NULL: 0)
+ *   nrm[i] = ||h||_2
+ *   o[i]   = h / max(||h||_2, 1e-12)
+ * o is f32 [N, H], contiguous, and nrm f32 [N]; both are stored once. bn_partial [n_slots, 2, H]
+ * receives per-slot f32 sums of o and o^2 over exactly the stored values, in the layout
+ * bgnn_bn_finalize reduces, with n_slots = bgnn_sage_fwd_bf16_slots(csr): one slot per light-row
+ * block of the kernel that will run, plus one per heavy row (every slot is written; the count is
+ * that of the grid, at least 8, also for a CSR without rows, whose call launches nothing and writes
+ * no slot; -1 for a NULL csr). bn_partial ==
+ * NULL skips the statistics (eval-mode BatchNorm with autograd on) and leaves o and nrm unchanged
+ * bit for bit. Light rows (deg <= csr->chunk) take the CSR's row-group plan (group_rows 4 or 8,
+ * chunk <= 64); a CSR without one takes one row per wave. Heavy rows use the chunk plan: f32 chunk
+ * sums into `partial` (n_chunks * H floats), combined in chunk order. No atomics: the summation
+ * order is fixed by the plan, so o, nrm and bn_partial are bit-identical run to run. The CSR's
+ * `ranges` are not used. BGNN_E_ARG, before anything is launched, when: H % 8 != 0 or H > 512;
+ * reduce is not SUM / MEAN; csr, z, o or nrm is NULL; ldz < 2H or ldz % 8 != 0; z, o, bias,
+ * bn_partial or partial is not 16-byte aligned; the CSR has chunks and partial is NULL or the chunk
+ * plan is incomplete. n_rows <= 0 returns BGNN_OK without a launch. */
+int32_t bgnn_sage_fwd_bf16_slots(const bgnn_csr_t* csr);
+int bgnn_sage_fwd_bf16(const bgnn_csr_t* csr, const void* z, int64_t ldz, const float* bias,
+                       int32_t H, int32_t reduce, float* o, float* nrm, float* bn_partial,
+                       float* partial, void* stream);
 
 /* Neighbour aggregation of bf16 rows and its transpose (ABI 15): bgnn_spmm_fwd / bgnn_spmm_bwd for
  * SUM and MEAN over bf16 storage -- the aggregation of the PyG surface (bgnn.ops.aggregate,
