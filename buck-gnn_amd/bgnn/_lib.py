@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BGNN_LIBRARY: a measurement build of the same ABI (make -C buck-gnn_amd m16), for tools/ only
 LIB_PATH = os.environ.get("BGNN_LIBRARY") or os.path.join(_HERE, "_lib", "libbgnn.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _lock = threading.Lock()
 _lib = None
@@ -113,6 +113,7 @@ SIGNATURES = {
     "bgnn_spmm_bwd_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_p, c_i64, c_i32, c_i32, c_p, c_i64, c_i32, c_p,
                                    c_p]),
     "bgnn_spmm_max_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p]),
+    "bgnn_spmm_max_pack_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p, c_p]),
     "bgnn_sage_tail_bf16": (c_i32, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_i64, c_i32, c_p]),
     "bgnn_rows_slots": (c_i32, [c_i64]),
     "bgnn_sage_bwd_stats": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f32, c_u64, c_i64, c_i32, c_p, c_p]),

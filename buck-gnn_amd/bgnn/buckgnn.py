@@ -42,7 +42,7 @@ FOLD_ENCODER = True
 # the batch vector instead of an [N, H] broadcast (A/B switch; the same bits)
 FUSED_POOL = True
 # default of BuckGNN.sage_bf16 for models built afterwards: the fused sum / mean SAGE layer loop
-# with autocast's rounding points (BuckGNN._sage_bf16_on)
+# with autocast's rounding points (BuckGNN._sage_bf16_on); "all": the max model too
 SAGE_BF16 = False
 
 _SAGE_VARIANTS = {
@@ -215,6 +215,9 @@ class BuckGNN(nn.Module):
         # dropout, the stored activations, all gradients and the decoder stay f32
         # (fused.sage_layer bf16=True). Off: the f32-accurate path. A shape outside the mode takes the
         # f32 path silently; infer_bf16 keeps precedence where it applies. (_sage_bf16_on)
+        # "all": as True, and GraphSage_maxAggr too -- aggregate-first, the maximum and its argmax from
+        # the f32 rows, [agg | x] and its two products stored as bf16 (fused._max_transform_bf16); under True
+        # a max model stays f32.
         # The encoder then runs whole and in f32 (no fold into layer 0).
         self.sage_bf16 = SAGE_BF16
         self._step = 0
@@ -288,10 +291,12 @@ class BuckGNN(nn.Module):
 
     def _sage_bf16_on(self, x: Tensor, aggr: str) -> bool:
         """Whether the fused SAGE layer loop runs with autocast's rounding points (sage_bf16): the
-        fused path on f32 input, a sum / mean aggregation and rows of whole 16-byte bf16 vectors."""
+        fused path on f32 input, a sum / mean aggregation (max too when the flag is "all") and rows
+        of whole 16-byte bf16 vectors."""
         h = self.hidden_channels
-        return bool(self.sage_bf16 and self._sage_fused(x, aggr) and aggr in ("add", "sum", "mean")
-                    and h % 8 == 0 and h <= 512)
+        # (max only under sage_bf16 == "all": True keeps the meaning it had before the max layer)
+        aggrs = ("add", "sum", "mean", "max") if self.sage_bf16 == "all" else ("add", "sum", "mean")
+        return bool(self.sage_bf16 and self._sage_fused(x, aggr) and aggr in aggrs and h % 8 == 0 and h <= 512)
 
     def _sage_loop_bf16(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, pool=None):
         """The eval-mode SAGE layer loop on bf16 rows: per layer one bf16 GEMM and one aggregation +

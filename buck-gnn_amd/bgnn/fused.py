@@ -638,8 +638,8 @@ class LayerConfig:
         # max pass (and no zero fill) of their own
         self.famax = None
         self.rng = None     # RangeRows (range rows of a stiffened batch) or None
-        # sum / mean layer with autocast's rounding points (sage_layer bf16=True): bf16 operands in
-        # the N-row products, z stored bf16, everything else f32
+        # layer with autocast's rounding points (sage_layer bf16=True): bf16 operands in the N-row
+        # products, z (max: [agg | x] and y) stored bf16, everything else f32
         self.bf16 = False
 
 
@@ -1076,6 +1076,82 @@ def _max_rows_fwd(y, b_l, H: int):
     return o, nrm, bn_part, slots
 
 
+def _max_transform_bf16(x, w_l, w_r, graph: Graph, name: str):
+    """_max_transform with autocast's rounding points (sage_layer bf16=True, reduce 2):
+        a = [bf16(agg) | bf16(x)]            bgnn_spmm_max_pack_bf16: the maximum and its argmax on the
+                                             f32 rows (the state _max_transform's gather would write),
+                                             rounded only where it is stored
+        y = [bf16(agg) W_l^T | bf16(x) W_r^T]   two bf16 MFMA products, K = C_in, each stored as bf16
+    The two terms are rounded apart, as autocast's two Linears round them (lin_l(agg) and lin_r(x) are
+    bf16 tensors before they are added): one product over K = 2 C_in with one rounding has a smaller
+    error of its own but another one than autocast's, and the prediction -- a few numbers behind a
+    mean pool -- then lands anywhere from 0.2 to 3 times autocast's distance from fp64 (DESIGN.md
+    section 3h). y is the [N, 2H] bf16 z of bgnn_sage_fwd_bf16, which adds its planes in f32 over
+    the identity CSR (_max_rows_fwd_bf16).
+    Returns (y, a, arg)."""
+    from .ops import spmm_max_pack_bf16
+    N = x.size(0)
+    H, C = w_l.shape
+    with _timed("agg_max"):
+        a, arg = spmm_max_pack_bf16(graph.fwd, x, N)
+    y = torch.empty(N, 2 * H, dtype=torch.bfloat16, device=x.device)
+    with _timed(name):
+        gemm_bf16(a[:, :C], w_l, trans_a=False, trans_b=True, out=y[:, :H])
+        gemm_bf16(a[:, C:], w_r, trans_a=False, trans_b=True, out=y[:, H:])
+    return y, a, arg
+
+
+def _max_rows_fwd_bf16(y, b_l, H: int, bn_stats: bool):
+    """_max_rows_fwd on the bf16 y = [y_l | y_r] of _max_transform_bf16: bgnn_sage_fwd_bf16 (sum)
+    over the identity CSR, h_i = (y_l[i] + y_r[i]) + b in f32 (bn_stats: the BatchNorm partial
+    sums, only where _glue_fwd reads them)."""
+    from .graph import identity_csr
+    N = y.size(0)
+    dev = y.device
+    if y.dtype != torch.bfloat16 or tuple(y.shape) != (N, 2 * H) or not y.is_contiguous():
+        raise ValueError("_max_rows_fwd_bf16: y must be a contiguous [N, 2H] bfloat16 tensor")
+    csr = identity_csr(N, dev)
+    o = torch.empty(N, H, dtype=torch.float32, device=dev)
+    nrm = torch.empty(N, dtype=torch.float32, device=dev)
+    slots = _lib.query("bgnn_sage_fwd_bf16_slots", csr.ref())
+    bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)
+    _lib.call("bgnn_sage_fwd_bf16", csr.ref(), y.data_ptr(), 2 * H, _ptr(b_l), H, 0,
+              o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr() if bn_stats else None, None, _stream())
+    return o, nrm, bn_part, slots
+
+
+def _max_backward_bf16(dh, wcat_t, a, arg, graph: Graph, gskip, need_dx: bool):
+    """_max_backward with bf16 operands in the N-row products (f32 accumulation and results):
+        [dagg | t] = dh [W_l | W_r]          one product; a skip layer takes two, dagg on its own and
+                                             t accumulated into gskip = drop(g) (beta = 1)
+        dx = A_max^T dagg + t                bgnn_spmm_bwd_max, f32, on the f32 argmax
+        [dW_l^T ; dW_r^T] = a^T dh           a = bf16 [agg | x], as the forward product read it
+    wcat_t = [W_l ; W_r]^T ([C, 2H])."""
+    N, H = dh.shape
+    C = a.size(1) // 2
+    dev = dh.device
+    dx = None
+    if need_dx:
+        with _timed("gemm_dgrad"):
+            if gskip is None:
+                wkt = torch.cat([wcat_t[:, :H], wcat_t[:, H:]], 0)      # [W_l^T ; W_r^T], [2C, H]
+                dt = gemm(dh, wkt, trans_a=False, trans_b=True, bf16=True)
+                dagg, t = dt[:, :C], dt[:, C:]
+            else:
+                dagg = gemm(dh, wcat_t[:, :H], trans_a=False, trans_b=True, bf16=True)
+                t = gemm(dh, wcat_t[:, H:], trans_a=False, trans_b=True, out=gskip, beta=1.0, bf16=True)
+        dx = torch.empty(N, C, dtype=torch.float32, device=dev)
+        bw = graph.bwd
+        part = torch.empty(bw.plan.n_chunks * C, dtype=torch.float32, device=dev) if bw.plan.n_chunks else None
+        with _timed("spmm_bwd"):
+            _lib.call("bgnn_spmm_bwd_max", bw.ref(), graph.perm_t.data_ptr(), graph.fwd.rowptr.data_ptr(), N,
+                      dagg.data_ptr(), dagg.stride(0), C, arg.data_ptr(), t.data_ptr(), t.stride(0),
+                      dx.data_ptr(), dx.stride(0), _ptr(part), None, _stream())
+    with _timed("gemm_wgrad"):
+        dwt = gemm_bf16(a, dh, trans_a=True, trans_b=False)              # [2C, H]
+    return dx, dwt[:C].t(), dwt[C:].t()
+
+
 def _max_backward(dh, dz_amax, wcat_t, x, agg, arg, graph: Graph, x_amax, w_amax, addend_beta_src,
                   need_dx: bool, p: float = 0.0, seed: int = 0):
     """Backward of y = [agg | x] [W_l | W_r]^T with agg = max-aggregate(x), given dh = dL/dy:
@@ -1176,12 +1252,23 @@ class SageMaxLayerFn(torch.autograd.Function):
             wcat_t = w1 if w1 is not None else w0.t().contiguous()
         else:
             wcat_t = torch.cat([w_l, w_r], 0).t().contiguous()
-            absmax(wcat_t, w_amax, accumulate=True)
-        if x_amax is None:
-            x_amax = absmax(x_prev)
-        y, agg, arg = _max_transform(x_prev, w_l, w_r, graph, x_amax, w_amax, "gemm_fwd_max")
-        with _timed("sage_fwd"):
-            o, nrm, bn_part, slots = _max_rows_fwd(y, b_l, H)
+            if not cfg.bf16:
+                absmax(wcat_t, w_amax, accumulate=True)
+        if cfg.bf16:
+            # autocast's rounding points: the bf16 products take no operand scale (a placeholder for
+            # the saved list); `agg` is a = bf16 [agg | x], which also stands in for x_prev in the
+            # weight gradient
+            if x_amax is None:
+                x_amax = torch.empty(0, dtype=torch.float32, device=dev)
+            y, agg, arg = _max_transform_bf16(x_prev, w_l, w_r, graph, "gemm_fwd_max")
+            with _timed("sage_fwd"):
+                o, nrm, bn_part, slots = _max_rows_fwd_bf16(y, b_l, H, cfg.bn and cfg.training)
+        else:
+            if x_amax is None:
+                x_amax = absmax(x_prev)
+            y, agg, arg = _max_transform(x_prev, w_l, w_r, graph, x_amax, w_amax, "gemm_fwd_max")
+            with _timed("sage_fwd"):
+                o, nrm, bn_part, slots = _max_rows_fwd(y, b_l, H)
         del y
         x_next, (scale, shift, mean, invstd), _ = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
                                                             running_var, cfg, next_amax)
@@ -1189,7 +1276,8 @@ class SageMaxLayerFn(torch.autograd.Function):
         ctx.cfg = cfg
         ctx.set_materialize_grads(False)
         e = torch.empty(0, device=dev)
-        ctx.save_for_backward(x_prev, agg, arg, o, nrm, wcat_t, gamma if gamma is not None else e,
+        # (bf16: a replaces both agg and x_prev in the products; the skip reads g, not x_prev)
+        ctx.save_for_backward(e if cfg.bf16 else x_prev, agg, arg, o, nrm, wcat_t, gamma if gamma is not None else e,
                               scale if scale is not None else e, shift if shift is not None else e,
                               mean if mean is not None else e, invstd if invstd is not None else e,
                               x_amax, w_amax, dz_amax)
@@ -1212,16 +1300,24 @@ class SageMaxLayerFn(torch.autograd.Function):
         dh = torch.empty(N, H, dtype=torch.float32, device=dev)
         rs = _lib.query("bgnn_rows_slots", N)
         part_db = torch.empty(rs, 2, H, dtype=torch.float32, device=dev)
+        # bf16: the products have no drop-add epilogue, so a skip layer's drop(g) is written by the
+        # row pass (gskip) and the dh W_r product accumulates into it
+        need_dx = ctx.needs_input_grad[0]
+        gskip = (torch.empty(N, H, dtype=torch.float32, device=dev) if (cfg.bf16 and cfg.skip and need_dx)
+                 else None)
         _lib.call("bgnn_sage_bwd_rows", g.data_ptr(), None, o.data_ptr(), nrm.data_ptr(),
                   _ptr(scale) if bn else None, _ptr(shift) if bn else None,
                   _ptr(gamma) if (bn and gamma.numel()) else None,
                   _ptr(mean) if bn else None, _ptr(invstd) if bn else None, _ptr(sum_g2), _ptr(sum_g2xhat),
-                  float(cfg.p), cfg.seed, 0, N, H, dh.data_ptr(), H, None, part_db.data_ptr(), dz_amax.data_ptr(),
-                  None, 0, None, None, None, s)
+                  float(cfg.p), cfg.seed, int(gskip is not None), N, H, dh.data_ptr(), H, _ptr(gskip),
+                  part_db.data_ptr(), dz_amax.data_ptr(), None, 0, None, None, None, s)
         db = torch.empty(H, dtype=torch.float32, device=dev)
         _lib.call("bgnn_reduce_partials", part_db.data_ptr(), rs, H, db.data_ptr(), None, 0, s)
-        dx, dw_l, dw_r = _max_backward(dh, dz_amax, wcat_t, x_prev, agg, arg, ctx.graph, x_amax, w_amax,
-                                       g if cfg.skip else None, ctx.needs_input_grad[0], cfg.p, cfg.seed)
+        if cfg.bf16:
+            dx, dw_l, dw_r = _max_backward_bf16(dh, wcat_t, agg, arg, ctx.graph, gskip, need_dx)
+        else:
+            dx, dw_l, dw_r = _max_backward(dh, dz_amax, wcat_t, x_prev, agg, arg, ctx.graph, x_amax, w_amax,
+                                           g if cfg.skip else None, need_dx, cfg.p, cfg.seed)
         has_affine = bn and gamma.numel() > 0
         return (dx, None, dw_l, db, dw_r, dgamma if has_affine else None, dbeta if has_affine else None,
                 None, None, None, None, None, None)
@@ -1348,11 +1444,14 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
     last element (SageLayerFn). need_x=False (with pool): the caller reads only the pool, so x_next
     is returned as None and, where the pooling apply pass runs, never written (nor is max|x_next|
     folded into the amax output then: it scales a GEMM that would read x_next).
-    bf16 (sum / mean, H % 8 == 0): autocast's rounding points -- the operands of the layer's N-row
+    bf16 (H % 8 == 0): autocast's rounding points -- the operands of the layer's N-row
     products (transform, dgrad, wgrad) are rounded to bf16 and z = x [W_l;W_r]^T is stored as bf16
     (bgnn_gemm_bf16, bgnn_sage_fwd_bf16); accumulators, bias, normalize, BatchNorm, ReLU, skip,
     dropout, the stored x / o / dh and every gradient stay f32. Range rows, pre-split weight images
-    and the operand maxima are not used then (rng is ignored), and w_in / b_in are refused."""
+    and the operand maxima are not used then (rng is ignored), and w_in / b_in are refused.
+    bf16 with reduce 2 (max): the layer stays aggregate-first -- the maximum and its argmax come from
+    the f32 rows (bgnn_spmm_max_pack_bf16), [agg | x] and the two terms of y = agg W_l^T + x W_r^T are
+    stored as bf16, the dgrad / wgrad products take bf16 operands (SageMaxLayerFn, _max_transform_bf16)."""
     require_cuda(x_prev, w_l, b_l, w_r, what="sage_layer")
     _require_f32(x_prev, "sage_layer")
     H = w_l.size(0)
@@ -1366,8 +1465,8 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
         raise ValueError("sage_layer: max aggregation needs its input rows (no folded input transform)")
     if reduce == 2 and pool is not None:
         raise ValueError("sage_layer: the fused mean pool is for sum / mean layers")
-    if bf16 and (reduce == 2 or H % 8):
-        raise ValueError(f"sage_layer: bf16 needs a sum / mean layer with H % 8 == 0 (got reduce {reduce}, H {H})")
+    if bf16 and H % 8:
+        raise ValueError(f"sage_layer: bf16 needs H % 8 == 0 (got H {H})")
     if bf16 and w_in is not None:
         raise ValueError("sage_layer: bf16 takes no folded input transform (w_in): the folded Linear would join "
                          "the layer's bf16 product")

@@ -313,6 +313,27 @@ def empty_csr(n_rows: int, device) -> Csr:
     return c
 
 
+_identity_csrs = {}
+
+
+def identity_csr(n_rows: int, device) -> Csr:
+    """The CSR of the identity (row i holds the one entry i; cached per size and device, no heavy rows,
+    no row-group plan). bgnn_sage_fwd_bf16 (sum) over it adds the two planes of z row by row,
+    h_i = (z_l[i] + z_r[i]) + b, and runs the SAGE row epilogue: the bf16 max-aggregation layer's
+    tail (bgnn.fused._max_rows_fwd_bf16)."""
+    key = (int(n_rows), str(device))
+    c = _identity_csrs.get(key)
+    if c is None:
+        if len(_identity_csrs) > 8:
+            _identity_csrs.clear()
+        dev = torch.device(device)
+        z = torch.zeros(1, dtype=torch.int32, device=dev)
+        plan = Plan(z, torch.zeros(2, dtype=torch.int32, device=dev), z, 0, 0, DEFAULT_CHUNK)
+        rowptr = torch.arange(n_rows + 1, dtype=torch.int32, device=dev)
+        c = _identity_csrs[key] = Csr(rowptr, rowptr, n_rows, n_rows, plan)
+    return c
+
+
 def graph_for(edge_index: torch.Tensor, num_nodes: int, chunk: int = DEFAULT_CHUNK) -> Graph:
     return _graph_cache.get(edge_index, (int(num_nodes), chunk),
                             lambda: Graph.build(edge_index, num_nodes, chunk))

@@ -154,6 +154,32 @@ def spmm_max_bf16(csr, x: torch.Tensor, out_rows: int, want_arg: bool = False, o
     return out, arg
 
 
+def spmm_max_pack_bf16(csr, x: torch.Tensor, out_rows: int, out: torch.Tensor = None):
+    """The max layer's bf16 GEMM operand from f32 rows in one pass (bgnn_spmm_max_pack_bf16):
+    a = [bf16(max over the CSR rows of x) | bf16(x)], the maximum and its argmax taken on the f32
+    values -- spmm_fwd(MAX)'s values rounded once, and its argmax state bit for bit. x: f32
+    [out_rows, H] with unit column stride, rows a multiple of 4 elements apart and a 16-byte aligned
+    base; out: a bf16 [out_rows, >= 2H] destination that satisfies _b16_rows (columns from 2H on
+    are left alone), or None for a new [out_rows, 2H]. Returns (a, arg): arg is the state spmm_bwd
+    reads and max_arg_positions decodes."""
+    require_cuda(x, what="spmm_max_pack_bf16")
+    H = x.size(1)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.size(0) != out_rows:
+        raise ValueError("spmm_max_pack_bf16: x must be float32 [out_rows, H] with unit column stride")
+    if out is None:
+        out = torch.empty(out_rows, 2 * H, dtype=torch.bfloat16, device=x.device)
+    elif (out.dtype != torch.bfloat16 or out.dim() != 2 or out.size(0) != out_rows or out.size(1) < 2 * H
+          or out.stride(1) != 1 or out.device != x.device):
+        raise ValueError("spmm_max_pack_bf16: out must be bfloat16 [out_rows, >= 2H] with unit column stride")
+    arg = torch.empty(_lib.query("bgnn_spmm_max_arg_bytes", out_rows, H, csr.plan.n_heavy), dtype=torch.uint8,
+                      device=x.device)
+    part = _partial(csr, H, 2, x.device)
+    if out_rows > 0:
+        _lib.call("bgnn_spmm_max_pack_bf16", csr.ref(), x.data_ptr(), x.stride(0), H, out.data_ptr(), out.stride(0),
+                  arg.data_ptr(), None if part is None else part.data_ptr(), _stream())
+    return out, arg
+
+
 class _AggregateMaxBf16(torch.autograd.Function):
     """max aggregation of bf16 rows on the bf16 kernel, output bf16 or its exact f32 widening. The
     backward is the f32 route's: the gradient upcast to f32, bgnn_spmm_bwd_max on the saved argmax

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 19
+#define BGNN_ABI_VERSION 20
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -467,6 +467,33 @@ int bgnn_spmm_bwd_bf16(const bgnn_csr_t* csr_t, const int32_t* fwd_rowptr, const
  * incomplete; arg with a chunk outside [1, 254]. n_rows <= 0 returns BGNN_OK without a launch. */
 int bgnn_spmm_max_bf16(const bgnn_csr_t* csr, const void* x, int64_t ldx, int32_t H,
                        void* out, int64_t ldo, void* arg, float* partial, void* stream);
+
+/* Max aggregation of f32 rows, packed as the bf16 A operands [agg | x] of the max layer's GEMMs
+ * (ABI 20; the bf16 training mode of GraphSage_maxAggr, BuckGNN.sage_bf16 = "all"):
+ *   out[r, 0:H)  = bf16(max_{e in row r} x[col[e], :])     plane 0
+ *   out[r, H:2H) = bf16(x[r, :])                            plane 1
+ * x: f32 [n_rows, ldx]; out: bf16 [n_rows, ldo], ldo >= 2H; ld* in elements. Both planes are
+ * rounded to nearest even and stored once; columns at and beyond 2H are not touched. The maximum
+ * and its argmax are taken on the f32 values with the semantics of bgnn_spmm_fwd(MAX): the
+ * accumulator starts at -inf, an edge replaces it only when strictly greater (the first maximising
+ * edge in CSR order wins, a NaN never wins; a column no edge won gives -inf), empty rows give 0.
+ * Rounding is monotone, so plane 0 equals bgnn_spmm_fwd(MAX)'s output rounded to bf16; the argmax
+ * is the f32 one, which a gather over rounded rows would not give (rows that tie in bf16 need not
+ * tie in f32). arg (required): the argmax state of bgnn_spmm_max_arg_bytes(n_rows, H, n_heavy) in
+ * the layout bgnn_spmm_bwd_max reads, under the state contract above (bgnn_spmm_fwd): every row
+ * with deg > 0 holds an offset in [0, deg) in every column, offset 0 for a column nothing won and
+ * for empty rows; heavy rows hold the marker byte, heavy_of and an int32 offset. csr->chunk must be
+ * in [1, 254]. Light rows (deg <= chunk) run one row per wave in CSR order. Heavy rows use the
+ * chunk plan: one wave per chunk writes `partial` (n_chunks * H floats followed by n_chunks * H
+ * int32 CSR positions, bgnn_spmm_fwd's rule), one wave per heavy row combines its chunks in chunk
+ * order with the same strict >. No atomics: bit-identical run to run. The CSR's `ranges` and its
+ * row-group plan are not used. BGNN_E_ARG, before anything is launched, when: csr, its rowptr, x,
+ * out or arg is NULL; H % 8 != 0, H < 8 or H > 512; ldx < H or ldx % 4 != 0; ldo < 2H or
+ * ldo % 8 != 0; x, out, arg or partial is not 16-byte aligned; the CSR has chunks and partial is
+ * NULL or the chunk plan is incomplete; chunk is outside [1, 254]. n_rows <= 0 returns BGNN_OK
+ * without a launch. */
+int bgnn_spmm_max_pack_bf16(const bgnn_csr_t* csr, const float* x, int64_t ldx, int32_t H,
+                            void* out, int64_t ldo, void* arg, float* partial, void* stream);
 
 /* The dense row tail of an eval-mode SAGE layer on bf16 rows (ABI 16): the tail of
  * bgnn_sage_infer_bf16 with a zero aggregate, for a layer whose y = [agg | x] [W_l | W_r]^T is
