@@ -127,6 +127,14 @@ def super_node_index(batch: Optional[Tensor], n_nodes: int, device) -> Tensor:
     return torch.cat([change, torch.tensor([batch.numel() - 1], device=batch.device)])
 
 
+def _bf16_aggrs(flag) -> tuple:
+    """The aggregations a bf16 flag (infer_bf16, sage_bf16) covers: none when off, sum / mean
+    under True, max too under "all" (True keeps the meaning it had before the max paths)."""
+    if not flag:
+        return ()
+    return ("add", "sum", "mean", "max") if flag == "all" else ("add", "sum", "mean")
+
+
 def _range_rows_on(graph, red: int, n_rows: int, H: int) -> bool:
     """Whether the fused sum / mean layer loop takes the range-row path (fused.RangeRows) on this
     graph: it has heavy rows, the row passes' blocks are short enough for the 3 range slots
@@ -282,10 +290,8 @@ class BuckGNN(nn.Module):
         of whole 16-byte bf16 vectors and BatchNorms with running statistics (their scale / shift
         are then known up front)."""
         h = self.hidden_channels
-        # (max only under infer_bf16 == "all": True keeps the meaning it had before the max path)
-        aggrs = ("add", "sum", "mean", "max") if self.infer_bf16 == "all" else ("add", "sum", "mean")
-        return bool(self.infer_bf16 and not self.training and not torch.is_grad_enabled()
-                    and self._fused_ok(x) and aggr in aggrs and h % 8 == 0 and h <= 512
+        return bool(aggr in _bf16_aggrs(self.infer_bf16) and not self.training and not torch.is_grad_enabled()
+                    and self._fused_ok(x) and h % 8 == 0 and h <= 512
                     and (bns is None or all(bn.track_running_stats and bn.running_mean is not None
                                             for bn in bns)))
 
@@ -294,9 +300,7 @@ class BuckGNN(nn.Module):
         fused path on f32 input, a sum / mean aggregation (max too when the flag is "all") and rows
         of whole 16-byte bf16 vectors."""
         h = self.hidden_channels
-        # (max only under sage_bf16 == "all": True keeps the meaning it had before the max layer)
-        aggrs = ("add", "sum", "mean", "max") if self.sage_bf16 == "all" else ("add", "sum", "mean")
-        return bool(self.sage_bf16 and self._sage_fused(x, aggr) and aggr in aggrs and h % 8 == 0 and h <= 512)
+        return bool(aggr in _bf16_aggrs(self.sage_bf16) and self._sage_fused(x, aggr) and h % 8 == 0 and h <= 512)
 
     def _sage_loop_bf16(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, pool=None):
         """The eval-mode SAGE layer loop on bf16 rows: per layer one bf16 GEMM and one aggregation +
@@ -467,17 +471,15 @@ class BuckGNN(nn.Module):
             real_node_batch = batch[is_real_node] if batch is not None else None
         x_amax = None   # max|x| after the encoder (f16x3 operand scale of the first SAGE GEMM)
         x_in = None     # the encoder's last Linear when it is folded into the first SAGE layer
-        sage = _SAGE_VARIANTS.get(name, (None, "add", None))[1] if name != "GraphSage_addAggr_Shared" else "add"
+        sage = _SAGE_VARIANTS.get(name, (None, "add", None))[1]
+        sage_loop = name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"   # a _sage_loop model
         # the bf16 inference loop takes the encoder's f32 output: the encoder stays unfolded
-        infer = ((name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared")
-                 and self._infer_bf16_on(x, sage, self.batch_norms if name in _SAGE_VARIANTS else None))
+        infer = sage_loop and self._infer_bf16_on(x, sage, self.batch_norms if name in _SAGE_VARIANTS else None)
         # sage_bf16 keeps the encoder f32 and whole: folded, its last Linear would join layer 0's bf16
         # product (h and [W_l;W_r] W_in rounded instead of x0 and [W_l;W_r]: not autocast's points)
-        unfold = ((name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared")
-                  and self._sage_bf16_on(x, sage))
+        unfold = sage_loop and self._sage_bf16_on(x, sage)
         # (GraphSAGE_SAG folds into sage_layers_1[0]: not when that list is empty, num_layers == 1)
-        if (name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"
-                or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) and not infer and not unfold \
+        if (sage_loop or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) and not infer and not unfold \
                 and self._sage_fused(x, sage) and sage != "max" and self._foldable_encoder(x):
             x_in = self.node_encoder[-1]
             x, x_amax = mlp(self.node_encoder[:-1], x, return_amax=True)
@@ -504,12 +506,14 @@ class BuckGNN(nn.Module):
                 x, e = self._skip_dropout(x, e, x_prev, e_prev, 0 < i < self.num_layers - 1, ea_fused)
         # the buckling decoder's mean pool from the last fused sum / mean layer (FUSED_POOL)
         pool = (batch_segments(batch) if (FUSED_POOL and self.prediction_type == "buckling"
-                                          and self.pooling_layer == "mean" and batch is not None
-                                          and (name == "GraphSage_addAggr_Shared" or name in _SAGE_VARIANTS)
+                                          and self.pooling_layer == "mean" and batch is not None and sage_loop
                                           and self._sage_fused(x, sage) and sage != "max") else None)
         pooled = None
-        if name == "GraphSage_addAggr_Shared":
-            x = self._sage_loop(x, edge_index, None, None, "add", True, x_amax, x_in, pool=pool)
+        if sage_loop:   # (the Shared variant: one conv for every layer, no BatchNorm)
+            per_layer = name in _SAGE_VARIANTS
+            convs = getattr(self, _SAGE_VARIANTS[name][0]) if per_layer else None
+            bns = self.batch_norms if per_layer else None
+            x = self._sage_loop(x, edge_index, convs, bns, sage, True, x_amax, x_in, pool=pool)
             if pool is not None:
                 x, pooled = x
         elif name == "EA_GNN":
@@ -525,12 +529,6 @@ class BuckGNN(nn.Module):
                 else:
                     x, e = blk(x, edge_index, e)
                 x, e = self._skip_dropout(x, e, x_prev, e_prev, 0 < i < L - 1, ea_fused, e_slot=slot)
-        elif name in _SAGE_VARIANTS:
-            attr, aggr, _ = _SAGE_VARIANTS[name]
-            x = self._sage_loop(x, edge_index, getattr(self, attr), self.batch_norms, aggr, True, x_amax, x_in,
-                                pool=pool)
-            if pool is not None:
-                x, pooled = x
         elif name in ("GraphSage_addAggr_woBatchNorm", "GraphSage_MLP"):
             getattr(self, "sage_blocks_add")  # AttributeError, as in the reference (:405,473)
         elif name == "GraphSage_sumAggr_woBatchNorm":

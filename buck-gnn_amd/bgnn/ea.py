@@ -29,7 +29,8 @@ import torch
 
 from . import _lib
 from . import fused
-from .fused import Pair, Planes, b16_weight, gemm, gemm_bf16, linear, linear_bf16, mlp, relu_bias_grad
+from .fused import (Pair, Planes, b16_weight, gemm, gemm_bf16, gemm_workspace, linear, linear_bf16, mlp,
+                    relu_bias_grad)
 from .graph import SegmentIndex, _index_cache, _stream
 from .ops import segment_reduce
 
@@ -93,8 +94,7 @@ class _LinearGatherReLU(torch.autograd.Function):
                    | (4 if out_bf16 else 0))
         out = torch.empty(M, N, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=e.device)
         prec = 1 if bf16 else 0
-        ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", M, N, K, 0, 1, prec)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=e.device) if ws_bytes else None
+        ws, ws_bytes = gemm_workspace(M, N, K, 0, 1, prec, e.device)
         args = (e.data_ptr(), e.stride(0), Wg.data_ptr(), Wg.stride(0), out.data_ptr(), N,
                 None if b is None else b.contiguous().data_ptr(), 1,
                 p1.data_ptr(), seg1.index.data_ptr(), p1.stride(0),
@@ -367,8 +367,7 @@ class _LinearResidual(torch.autograd.Function):
         W = weight.contiguous()
         out = torch.empty(M, N, dtype=torch.float32, device=h.device)
         idx = _identity_index(M, h.device)
-        ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", M, N, K, 0, 1, 1)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=h.device) if ws_bytes else None
+        ws, ws_bytes = gemm_workspace(M, N, K, 0, 1, 1, h.device)
         _lib.call("bgnn_gemm_gather_add", 0, 1, M, N, K, h.data_ptr(), h.stride(0), W.data_ptr(), W.stride(0),
                   out.data_ptr(), N, None if bias is None else bias.contiguous().data_ptr(), 0,
                   r.data_ptr(), idx.data_ptr(), r.stride(0), None, None, 0, 1,

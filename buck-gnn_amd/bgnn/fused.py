@@ -22,6 +22,7 @@ import torch
 
 from . import _lib
 from .graph import Graph, _stream, require_cuda
+from .ops import _ptr, spmm_bwd_into, spmm_bwd_max_into
 
 # "hip" = bgnn_gemm_f32 (hand-written f32 MFMA); "torch" = torch.mm (rocBLAS/hipBLASLt),
 # kept only for A/B measurement. Both run on the GPU.
@@ -36,16 +37,11 @@ GEMM_BACKEND = "hip"
 PLANE_TILE = 128
 Z_PLANES = False
 DZ_PLANES = False
-# dgrad B operand: transposed copy of [W_l;W_r] (K-contiguous loads) instead of strided reads
-DGRAD_WT = True
 # folded input transform: the weight-by-weight products (Wf = Wcat W_in, its gradients; no node
-# dimension, <= 0.3 GFLOP each) on torch.mm instead of bgnn_gemm (A/B switch; default bgnn:
-# both are f32-class, torch.mm saved ~1 % of the step but shifts the BN-amplified gradient
-# rounding noise, tools/fold_ab.py)
-FOLD_WEIGHTS_TORCH = False
-# ... in the grouped native launches of csrc/fold.hip (bgnn_fold_weights_fwd / _bwd: one or two
-# launches per direction instead of ~7, bit-identical to the bgnn_gemm chain, which stays as the
-# fallback for shapes the planner does not put on the 128 x 128 f16x3 tile; A/B switch)
+# dimension, <= 0.3 GFLOP each) in the grouped native launches of csrc/fold.hip
+# (bgnn_fold_weights_fwd / _bwd: one or two launches per direction instead of ~7, bit-identical
+# to the bgnn_gemm chain, which stays as the fallback for shapes the planner does not put on the
+# 128 x 128 f16x3 tile; A/B switch)
 FOLD_NATIVE = True
 # skip layers' dgrad adds the dropout-masked incoming gradient in its epilogue
 # (bgnn_gemm_f32_dropadd) instead of reading a skip gradient bgnn_sage_bwd_rows wrote
@@ -54,8 +50,6 @@ DGRAD_DROPADD = True
 # bf16-stored Linear backward (EA_GNN's bf16 configuration): ReLU mask + f32 bias-gradient sums
 # in one bgnn pass (bgnn_linear_bwd_prep_bf16) instead of torch threshold_backward + sum (A/B switch)
 BF16_PREP = True
-# per-layer weight maxima of a SAGE layer loop in one launch (bgnn_absmax_items_f32)
-ABSMAX_ITEMS = True
 # [W_l;W_r] of all layers packed by a multi-tensor copy into a persistent buffer (not torch.cat)
 PERSISTENT_WPACK = True
 # max aggregation: the two input-gradient products as one GEMM [dh W_l | dh W_r (+ drop(g))] and
@@ -83,7 +77,7 @@ class _timed:
         self.ev = None
 
     def __enter__(self):
-        if TIMERS is not None:
+        if TIMERS is not None and self.name is not None:   # (a launcher called without a timer key)
             mk = TIMER_EVENT or (lambda: torch.cuda.Event(enable_timing=True))
             self.ev = (mk(), mk())
             self.ev[0].record()
@@ -149,6 +143,29 @@ def _operand(x):
     return x.data_ptr(), x.stride(0), 0, 0
 
 
+def _saved(t, dev):
+    """t, or an empty placeholder for None (save_for_backward takes tensors only)."""
+    return t if t is not None else torch.empty(0, device=dev)
+
+
+def _workspace(nbytes: int, dev):
+    """A kernel's scratch of nbytes bytes (None for 0)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+
+
+def gemm_workspace(M: int, N: int, K: int, trans_a, trans_b, prec: int, dev):
+    """(ws, ws_bytes): the split-K scratch of an M x N x K bgnn GEMM (prec 0: f32-accurate,
+    1: bf16 operands), which every GEMM entry point takes as its last two arguments."""
+    ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", M, N, K, int(trans_a), int(trans_b), prec)
+    return _workspace(ws_bytes, dev), ws_bytes
+
+
+def reduce_partials(part: torch.Tensor, slots: int, C: int, out0: torch.Tensor, out1: torch.Tensor = None):
+    """Column sums over the slots of a row pass's [slots, 2, C] partials: plane 0 into out0 and,
+    where given, plane 1 into out1 (bgnn_reduce_partials)."""
+    _lib.call("bgnn_reduce_partials", part.data_ptr(), slots, C, out0.data_ptr(), _ptr(out1), 0, _stream())
+
+
 def absmax(x: torch.Tensor, out: torch.Tensor = None, accumulate: bool = False) -> torch.Tensor:
     """max |x| of a row-major fp32 matrix (unit column stride) into a 1-element device tensor
     (bgnn_absmax_f32; accumulate folds into out's current value)."""
@@ -202,12 +219,10 @@ def gemm(a, b: torch.Tensor, trans_a: bool, trans_b: bool, out=None, beta: float
     pb, ldb, _, _ = _operand(b)
     pc, ldc, c_blk, c_ps = _operand(out)
     prec = 1 if bf16 else 0
-    ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", M, N, K, int(trans_a), int(trans_b), prec)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=b.device) if ws_bytes else None
+    ws, ws_bytes = gemm_workspace(M, N, K, trans_a, trans_b, prec, b.device)
     _lib.call("bgnn_gemm_f32_scaled", int(trans_a), int(trans_b), M, N, K, float(alpha), pa, lda, a_blk, a_ps,
-              pb, ldb, float(beta), pc, ldc, c_blk, c_ps, None if bias is None else bias.data_ptr(), int(relu),
-              _ptr(a_amax), _ptr(b_amax), _ptr(c_amax), prec, None if ws is None else ws.data_ptr(), ws_bytes,
-              _stream())
+              pb, ldb, float(beta), pc, ldc, c_blk, c_ps, _ptr(bias), int(relu),
+              _ptr(a_amax), _ptr(b_amax), _ptr(c_amax), prec, _ptr(ws), ws_bytes, _stream())
     return out
 
 
@@ -248,8 +263,7 @@ def gemm_bf16(a: torch.Tensor, b: torch.Tensor, trans_a: bool, trans_b: bool, ou
                | (4 if out.dtype == torch.bfloat16 else 0))
     if storage not in _BF16_BUILT.get((int(trans_a), int(trans_b)), (0,)):
         raise ValueError(f"gemm_bf16: storage {storage} with trans_a={trans_a}, trans_b={trans_b} is not built")
-    ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", M, N, K, int(trans_a), int(trans_b), 1)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=b.device) if ws_bytes else None
+    ws, ws_bytes = gemm_workspace(M, N, K, trans_a, trans_b, 1, b.device)
     _lib.call("bgnn_gemm_bf16", int(trans_a), int(trans_b), M, N, K, 1.0, a.data_ptr(), a.stride(0), b.data_ptr(),
               b.stride(0), 0.0, out.data_ptr(), out.stride(0), _ptr(bias), int(relu), storage, _ptr(ws), ws_bytes,
               _stream())
@@ -267,7 +281,7 @@ class LinearBf16Fn(torch.autograd.Function):
         x = x.contiguous()
         y = gemm_bf16(x, weight.contiguous(), False, True, out_bf16=out_bf16, bias=bias, relu=relu)
         ctx.relu, ctx.has_bias = relu, bias is not None
-        ctx.save_for_backward(x, weight, y if relu else torch.empty(0, device=x.device))
+        ctx.save_for_backward(x, weight, _saved(y if relu else None, x.device))
         return y
 
     @staticmethod
@@ -327,13 +341,12 @@ def relu_bias_grad_bf16(g: torch.Tensor, y=None, bias: bool = True):
     gm = torch.empty_like(g) if y is not None else g
     slots = _lib.query("bgnn_linear_bwd_prep_slots")
     part = torch.empty(slots, 2, C, dtype=torch.float32, device=g.device)
-    s = _stream()
-    _lib.call("bgnn_linear_bwd_prep_bf16", g.data_ptr(), None if y is None else y.data_ptr(), g.size(0), C,
-              gm.data_ptr() if y is not None else None, part.data_ptr(), s)
+    _lib.call("bgnn_linear_bwd_prep_bf16", g.data_ptr(), _ptr(y), g.size(0), C,
+              gm.data_ptr() if y is not None else None, part.data_ptr(), _stream())
     db = None
     if bias:
         db = torch.empty(C, dtype=torch.float32, device=g.device)
-        _lib.call("bgnn_reduce_partials", part.data_ptr(), slots, C, db.data_ptr(), None, 0, s)
+        reduce_partials(part, slots, C, db)
     return gm, db
 
 
@@ -349,13 +362,12 @@ def relu_bias_grad(g: torch.Tensor, y=None, bias: bool = True):
         slots = _lib.query("bgnn_linear_bwd_prep_slots")
         part = torch.empty(slots, 2, C, dtype=torch.float32, device=g.device)
         g_amax = torch.zeros(1, dtype=torch.float32, device=g.device)
-        s = _stream()
-        _lib.call("bgnn_linear_bwd_prep", g.data_ptr(), None if y is None else y.data_ptr(), g.size(0), C,
-                  gm.data_ptr() if y is not None else None, part.data_ptr(), g_amax.data_ptr(), s)
+        _lib.call("bgnn_linear_bwd_prep", g.data_ptr(), _ptr(y), g.size(0), C,
+                  gm.data_ptr() if y is not None else None, part.data_ptr(), g_amax.data_ptr(), _stream())
         db = None
         if bias:
             db = torch.empty(C, dtype=torch.float32, device=g.device)
-            _lib.call("bgnn_reduce_partials", part.data_ptr(), slots, C, db.data_ptr(), None, 0, s)
+            reduce_partials(part, slots, C, db)
         return gm, db, g_amax
     if y is not None:
         g = torch.ops.aten.threshold_backward(g, y, 0.0)   # ReLU mask in one pass
@@ -383,8 +395,7 @@ class LinearFn(torch.autograd.Function):
         ctx.relu = relu
         ctx.bf16 = bf16
         ctx.has_bias = bias is not None
-        ctx.save_for_backward(x, weight, y if relu else torch.empty(0, device=x.device),
-                              x_amax if x_amax is not None else torch.empty(0, device=x.device), w_amax)
+        ctx.save_for_backward(x, weight, _saved(y if relu else None, x.device), _saved(x_amax, x.device), w_amax)
         ctx.mark_non_differentiable(y_amax)
         ctx.set_materialize_grads(False)   # no zero-filled gradient for y_amax
         return y, y_amax
@@ -402,11 +413,9 @@ class LinearFn(torch.autograd.Function):
         x_amax = None if bf16 else x_amax
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = (gemm(g, weight.t().contiguous(), trans_a=False, trans_b=True, a_amax=g_amax, b_amax=w_amax,
-                       bf16=bf16)
-                  if DGRAD_WT else
-                  gemm(g, weight.contiguous(), trans_a=False, trans_b=False, a_amax=g_amax, b_amax=w_amax,
-                       bf16=bf16))
+            # (W transposed once so the dgrad reads its B operand K-contiguous)
+            dx = gemm(g, weight.t().contiguous(), trans_a=False, trans_b=True, a_amax=g_amax, b_amax=w_amax,
+                      bf16=bf16)
         dw = gemm(g, x, trans_a=True, trans_b=False, a_amax=g_amax, b_amax=x_amax, bf16=bf16)
         return dx, dw, db, None, None, None, None
 
@@ -592,10 +601,6 @@ def mlp(seq: torch.nn.Sequential, x: torch.Tensor, return_amax: bool = False, bf
     return (x, amax) if return_amax else x
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class RangeRows:
     """Range-row plumbing of one fused sum / mean layer (csrc/ranges.hip; Csr.ensure_ranges): the
     super nodes of a stiffened batch (VirtualEdgeCreate.py:81-113) aggregate their graph's whole
@@ -624,23 +629,26 @@ class LayerConfig:
     __slots__ = ("reduce", "bn", "training", "momentum", "eps", "skip", "p", "seed", "famax", "rng", "bf16")
 
     def __init__(self, reduce: int, bn: bool, training: bool, momentum: float, eps: float, skip: bool,
-                 p: float, seed: int):
+                 p: float, seed: int, *, dropout: bool = None, famax=None, rng=None, bf16: bool = False):
         self.reduce = reduce
         self.bn = bn
+        # `training` selects the BatchNorm batch statistics (a module that tracks no running
+        # statistics uses them in eval mode too); `dropout` (default: training) whether the
+        # dropout is active, which follows the module's mode alone
         self.training = training
         self.momentum = momentum
         self.eps = eps
         self.skip = skip
-        self.p = p if training else 0.0
+        self.p = p if (training if dropout is None else dropout) else 0.0
         self.seed = seed
         # folded layer: 5 zeroed device slots for the maxima of the weight-product operands
         # (max|Wcat|, max|W_in|, max|b_in|, max|dWf|, max|dbf|), so those small f16x3 GEMMs need no
         # max pass (and no zero fill) of their own
-        self.famax = None
-        self.rng = None     # RangeRows (range rows of a stiffened batch) or None
+        self.famax = famax
+        self.rng = rng      # RangeRows (range rows of a stiffened batch) or None
         # layer with autocast's rounding points (sage_layer bf16=True): bf16 operands in the N-row
         # products, z (max: [agg | x] and y) stored bf16, everything else f32
-        self.bf16 = False
+        self.bf16 = bf16
 
 
 _E_ARG = 1001   # BGNN_E_ARG (include/bgnn.h)
@@ -726,13 +734,12 @@ def _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg: LayerConfig, g_rows=N
         return None, None, None, None
     N, H = o.shape
     dev = o.device
-    s = _stream()
     rs = _lib.query("bgnn_rows_slots", N)
     part2 = torch.empty(rs, 2, H, dtype=torch.float32, device=dev)
     _lib.call("bgnn_sage_bwd_stats", g.data_ptr(), _ptr(g_rows), o.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-              mean.data_ptr(), invstd.data_ptr(), float(cfg.p), cfg.seed, N, H, part2.data_ptr(), s)
+              mean.data_ptr(), invstd.data_ptr(), float(cfg.p), cfg.seed, N, H, part2.data_ptr(), _stream())
     sums = torch.empty(2, H, dtype=torch.float32, device=dev)
-    _lib.call("bgnn_reduce_partials", part2.data_ptr(), rs, H, sums[0].data_ptr(), sums[1].data_ptr(), 0, s)
+    reduce_partials(part2, rs, H, sums[0], sums[1])
     dbeta, dgamma = sums[0], sums[1]
     if cfg.training:
         return dgamma, dbeta, sums[0], sums[1]
@@ -749,9 +756,235 @@ def _fold_native_ok(famax, wcat, w_in, b_in) -> bool:
                 and _lib.query("bgnn_fold_weights_supported", wcat.size(1), w_in.size(1)))
 
 
+def _fold_fwd(wcat, w_in, b_in, famax, w_amax):
+    """The folded layer 0's weight chain: the encoder's last Linear folded into the transform
+    (x = h W_in^T + b_in never materialised), z = x [W_l;W_r]^T = h Wf^T + bf with
+    Wf = [W_l;W_r] W_in [2H, K_in] and bf = [W_l;W_r] b_in; max|Wf| is folded into w_amax.
+    famax: LayerConfig.famax (slots 0..2: max|Wcat|, max|W_in|, max|b_in|) or None.
+    Returns (wf, bf, wf_t): wf_t = Wf^T (the dgrad operand) from the native launch
+    (bgnn_fold_weights_fwd), None from the bgnn_gemm chain."""
+    H, K_in = w_in.shape
+    dev = wcat.device
+    if _fold_native_ok(famax, wcat, w_in, b_in):   # (folds max|Wf| in itself)
+        wf = torch.empty(2 * H, K_in, dtype=torch.float32, device=dev)
+        bf = torch.empty(2 * H, dtype=torch.float32, device=dev)
+        wf_t = torch.empty(K_in, 2 * H, dtype=torch.float32, device=dev)
+        _lib.call("bgnn_fold_weights_fwd", H, K_in, wcat.data_ptr(), wcat.stride(0), w_in.data_ptr(),
+                  w_in.stride(0), b_in.data_ptr(), famax.data_ptr(), wf.data_ptr(), K_in, bf.data_ptr(),
+                  wf_t.data_ptr(), 2 * H, w_amax.data_ptr(), _stream())
+        return wf, bf, wf_t
+    fa = (None, None, None)
+    if famax is not None:   # the same maxima the GEMMs would compute, without their fills
+        fa = (famax[0:1], famax[1:2], famax[2:3])
+        absmax(wcat, fa[0], accumulate=True)
+        absmax(w_in, fa[1], accumulate=True)
+        absmax(b_in.view(1, -1), fa[2], accumulate=True)
+    wf = gemm(wcat, w_in.contiguous(), trans_a=False, trans_b=False, a_amax=fa[0], b_amax=fa[1])
+    # (bgnn GEMM, not torch.mv: rocBLAS's GEMV moved the BN-amplified gradients of the
+    # Shared variant 50x further from fp64, tests/test_gpu_fold.py)
+    bf = gemm(wcat, b_in.contiguous().view(H, 1), trans_a=False, trans_b=False, a_amax=fa[0],
+              b_amax=fa[2]).view(-1)
+    absmax(wf, w_amax, accumulate=True)
+    return wf, bf, None
+
+
+def _fold_bwd(dwf, db2, wcat, w_in, b_in, famax):
+    """Backward of _fold_fwd from dWf = dz^T h [2H, K_in] (max|dWf| in famax[3]) and dbf = db2
+    viewed flat ([Σ dz_l ; Σ dh]): dWcat = dWf W_in^T + dbf b_in^T (= dz^T x) [2H, H],
+    dW_in = Wcat^T dWf [H, K_in], db_in = Wcat^T dbf [H], on bgnn_fold_weights_bwd or the
+    bgnn_gemm chain. Returns (dWcat, dW_in, db_in)."""
+    H, K_in = w_in.shape
+    dev = dwf.device
+    dbf = db2.view(-1)
+    if _fold_native_ok(famax, wcat, w_in, b_in) and dwf.stride(1) == 1:   # (folds max|dbf| in itself)
+        dw = torch.empty(2 * H, H, dtype=torch.float32, device=dev)
+        dw_in = torch.empty(H, K_in, dtype=torch.float32, device=dev)
+        db_in = torch.empty(H, dtype=torch.float32, device=dev)
+        ws_bytes = _lib.query("bgnn_fold_weights_ws_bytes", H, K_in)
+        ws = _workspace(ws_bytes, dev)
+        _lib.call("bgnn_fold_weights_bwd", H, K_in, dwf.data_ptr(), dwf.stride(0), dbf.data_ptr(),
+                  wcat.data_ptr(), wcat.stride(0), w_in.data_ptr(), w_in.stride(0), b_in.data_ptr(),
+                  famax.data_ptr(), dw.data_ptr(), H, dw_in.data_ptr(), K_in, db_in.data_ptr(), _ptr(ws),
+                  ws_bytes, _stream())
+        return dw, dw_in, db_in
+    a_wcat = a_win = a_dwf = a_dbf = None
+    if famax is not None:
+        a_wcat, a_win, a_dwf, a_dbf = famax[0:1], famax[1:2], famax[3:4], famax[4:5]
+        absmax(db2, a_dbf, accumulate=True)
+    dw = gemm(dwf, w_in.contiguous(), trans_a=False, trans_b=True, a_amax=a_dwf, b_amax=a_win)
+    dw.add_(torch.outer(dbf, b_in))
+    dw_in = gemm(wcat, dwf, trans_a=True, trans_b=False, a_amax=a_wcat, b_amax=a_dwf)
+    db_in = gemm(wcat, dbf.view(-1, 1), trans_a=True, trans_b=False, a_amax=a_wcat, b_amax=a_dbf).view(-1)
+    return dw, dw_in, db_in
+
+
+def _gemm_w(a, img, bn: int, N: int, a_amax, b_amax, g=None, ldg: int = 0, p: float = 0.0, seed: int = 0,
+            timer: str = None):
+    """C = a W^T [M, N] with W given as its pre-split image (WPrep img_f / img_d with column tile
+    bn; bgnn_gemm_f32_w, bit-identical to gemm on the f32 W); g (ld ldg): drop_p(g) added in the
+    epilogue, as _gemm_dropadd does. timer: the TIMERS key of the launch (the launchers that take
+    one bracket the launch alone, not their allocations and queries)."""
+    M, K = a.shape
+    out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    with _timed(timer):
+        _lib.call("bgnn_gemm_f32_w", M, N, K, a.data_ptr(), a.stride(0), img.data_ptr(), bn, out.data_ptr(), N, None,
+                  0, a_amax.data_ptr(), b_amax.data_ptr(), None, _ptr(g), ldg, float(p), seed, _stream())
+    return out
+
+
+def _gemm_dropadd(a, bt, a_amax, b_amax, g, p: float, seed: int, timer: str = None):
+    """C = a bt^T + drop_p(g) [M, N]: the skip connection's incoming gradient g added through the
+    layer's counter-based dropout mask in the GEMM epilogue (bgnn_gemm_f32_dropadd)."""
+    M, K = a.shape
+    N = bt.size(0)
+    out = torch.empty(M, N, dtype=torch.float32, device=a.device)
+    ws, ws_bytes = gemm_workspace(M, N, K, 0, 1, 0, a.device)
+    with _timed(timer):
+        _lib.call("bgnn_gemm_f32_dropadd", 0, 1, M, N, K, a.data_ptr(), a.stride(0), bt.data_ptr(), bt.stride(0),
+                  out.data_ptr(), out.stride(0), a_amax.data_ptr(), b_amax.data_ptr(), g.data_ptr(), g.stride(0),
+                  float(p), seed, _ptr(ws), ws_bytes, _stream())
+    return out
+
+
+def _sage_rows_fwd(csr, zl, zr, bias, H: int, reduce: int, bn_stats: bool = True, heavy_agg=None,
+                   timer: str = None):
+    """The SAGE row epilogue over csr: o_i = normalize(AGG_{j->i} z_l[j] + z_r[i] + bias), its row
+    norms and the per-slot BatchNorm partial sums of o.
+    f32 (bgnn_sage_fwd): zl / zr address the [*, H] halves of z by data pointer and row stride (an
+    interleaved z itself serves as zl); bias a tensor; heavy_agg: the heavy rows' aggregates
+    ([n_heavy, *] rows, RangeRows) instead of their chunk pass.
+    bf16 (bgnn_sage_fwd_bf16; zl a bfloat16 [*, 2H] = [z_l | z_r], zr None): bias may be None, and
+    the partial sums are written only with bn_stats (the f32 kernel always writes them).
+    Returns (o, nrm, bn_part, slots)."""
+    N = csr.n_rows
+    dev = zl.device
+    b16 = zl.dtype == torch.bfloat16
+    o = torch.empty(N, H, dtype=torch.float32, device=dev)
+    nrm = torch.empty(N, dtype=torch.float32, device=dev)
+    slots = _lib.query("bgnn_sage_fwd_bf16_slots" if b16 else "bgnn_sage_fwd_slots", csr.ref())
+    bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)
+    part = torch.empty(csr.plan.n_chunks * H, dtype=torch.float32, device=dev) if csr.plan.n_chunks else None
+    with _timed(timer):
+        if b16:
+            _lib.call("bgnn_sage_fwd_bf16", csr.ref(), zl.data_ptr(), zl.stride(0), _ptr(bias), H, reduce,
+                      o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr() if bn_stats else None, _ptr(part), _stream())
+        else:
+            _lib.call("bgnn_sage_fwd", csr.ref(), zl.data_ptr(), zl.stride(0), zr.data_ptr(), zr.stride(0),
+                      bias.data_ptr(), H, reduce, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), _ptr(part),
+                      _ptr(heavy_agg), heavy_agg.stride(0) if heavy_agg is not None else 0, _stream())
+    return o, nrm, bn_part, slots
+
+
+def _sage_rows_bwd(g, g_rows, o, nrm, gamma, coeffs, sums, cfg: LayerConfig, dh, dz_amax, gskip=None,
+                   graph: Graph = None, folded: bool = False, range_dzl=None):
+    """The backward row pass (bgnn_sage_bwd_rows): dropout, skip, ReLU, BatchNorm and normalize
+    backward of every row, dh written into `dh` ([N, H], any row stride), max|dh| folded into
+    dz_amax; gskip ([N, H] or None): also write the skip gradient drop(g) there.
+    coeffs = (scale, shift, mean, invstd) and sums = (sum_g2, sum_g2xhat) from the forward glue and
+    _glue_bwd_stats (ignored without BatchNorm); g_rows: see _glue_bwd_stats.
+    folded (needs graph): the pass also sums dz_l = A^T dh per column from the in-degrees.
+    range_dzl (needs graph; RangeRows): the pass sums dh over each transposed range row's targets
+    and bgnn_range_sums_finish writes those dz_l rows into range_dzl.
+    Returns db2: [1, H] = Σ dh (db_l), or folded [2, H] = [Σ dz_l ; Σ dh], which flat is dbf."""
+    N, H = o.shape
+    dev = o.device
+    s = _stream()
+    scale, shift, mean, invstd = coeffs if cfg.bn else (None,) * 4
+    rs = _lib.query("bgnn_rows_slots", N)
+    part_db = torch.empty(rs, 2, H, dtype=torch.float32, device=dev)
+    bw = graph.bwd if range_dzl is not None else None
+    rp = (torch.empty(_lib.query("bgnn_range_partial_bytes", N, H) // 4, dtype=torch.float32, device=dev)
+          if bw is not None else None)
+    _lib.call("bgnn_sage_bwd_rows", g.data_ptr(), _ptr(g_rows), o.data_ptr(), nrm.data_ptr(), _ptr(scale),
+              _ptr(shift), _ptr(gamma) if (cfg.bn and gamma.numel()) else None, _ptr(mean), _ptr(invstd),
+              _ptr(sums[0]), _ptr(sums[1]), float(cfg.p), cfg.seed, int(gskip is not None), N, H, dh.data_ptr(),
+              dh.stride(0), _ptr(gskip), part_db.data_ptr(), dz_amax.data_ptr(),
+              graph.fwd.rowptr.data_ptr() if folded else None, (2 if cfg.reduce == 1 else 1) if folded else 0,
+              _ptr(bw.ranges) if bw is not None else None,
+              graph.fwd.rowptr.data_ptr() if (bw is not None and cfg.reduce == 1) else None, _ptr(rp), s)
+    if bw is not None:   # the super nodes' dz_l rows (and their max |.| into dz_amax)
+        _lib.call("bgnn_range_sums_finish", rp.data_ptr(), N, H, bw.ref(), 1, range_dzl.data_ptr(),
+                  range_dzl.stride(0), None, dz_amax.data_ptr(), s)
+    db2 = torch.empty(2 if folded else 1, H, dtype=torch.float32, device=dev)
+    reduce_partials(part_db, rs, H, db2[-1], db2[0] if folded else None)
+    return db2
+
+
+def _pool_grad(g, g_pool, seg, skip: bool):
+    """The gradient of a layer whose mean pool was an output (SageLayerFn pool): (g, g_rows) with
+    the pooled gradient / count (bgnn.ops._SegmentReduce.backward) either read through the batch
+    vector (g_rows: row r's gradient is row g_rows[r] of g) or, where x_next has a gradient of its
+    own or the skip reads g by row, broadcast and added."""
+    if g_pool is None:
+        return g, None
+    # one launch with the bits of g_pool / seg.fwd.degree().clamp_min(1).to(float32).unsqueeze(1)
+    gpc = g_pool.contiguous()
+    gp = torch.empty_like(gpc)
+    _lib.call("bgnn_pool_grad_scale", gpc.data_ptr(), seg.fwd.rowptr.data_ptr(), gpc.size(0), gpc.size(1),
+              gp.data_ptr(), _stream())
+    if g is None and not skip:
+        return gp, seg.index
+    gb = gp.index_select(0, seg.index)
+    return (gb if g is None else g + gb), None
+
+
+def _sage_transform(x_prev, x_amax, wmat, bf, w_amax, cfg: LayerConfig, img, folded: bool):
+    """Step 1 of the layer, z = x_prev wmat^T (+ bf): returns (zl, zr, heavy_agg) as
+    _sage_rows_fwd takes them. The layout of z is decided here: bf16 [N, 2H] (cfg.bf16), two dense
+    [N, H] planes (Z_PLANES), else interleaved [M, 2H] -- with range rows (RangeRows) x_prev is the
+    head of an [N + R, H] buffer whose last R rows are the range sums of x_prev, the GEMM runs on
+    all M = N + R rows and z_l's extra rows are the range rows' aggregates (heavy_agg).
+    img: the layer's WPrep with a pre-split [W_l;W_r] image, or None."""
+    N = x_prev.size(0)
+    H = wmat.size(0) // 2
+    # (the folded layer's transform has K = K_in, not H: timed under its own name so the
+    # bench's flops per launch are right for every launch it averages)
+    name = "gemm_fwd_fold" if folded else "gemm_fwd"
+    if cfg.bf16:   # operands rounded to bf16 in-tile, z stored bf16 (bgnn_gemm_bf16 storage 4)
+        with _timed(name):
+            return gemm_bf16(x_prev, wmat, trans_a=False, trans_b=True, out_bf16=True), None, None
+    if Z_PLANES and H % PLANE_TILE == 0 and not folded:
+        z = torch.empty(2, N, H, dtype=torch.float32, device=x_prev.device)
+        with _timed(name):
+            gemm(x_prev, wmat, trans_a=False, trans_b=True, out=Planes(z), a_amax=x_amax, b_amax=w_amax)
+        return z[0], z[1], None
+    rng = cfg.rng
+    xa, a_amax = x_prev, x_amax
+    full = rng is not None and rng.x_full is not None and not folded
+    if full:
+        if rng.x_full.data_ptr() != x_prev.data_ptr():
+            raise RuntimeError("sage_layer: RangeRows.x_full must start at x_prev")
+        xa, a_amax = rng.x_full, rng.x_amax
+    pre = img is not None and not folded and _lib.query("bgnn_gemm_w_tile", xa.size(0), 2 * H, H) == img.bn_f
+    with _timed(name):
+        if pre:
+            z = _gemm_w(xa, img.img_f, img.bn_f, 2 * H, a_amax, w_amax)
+        else:
+            z = gemm(xa, wmat, trans_a=False, trans_b=True, bias=bf, a_amax=a_amax, b_amax=w_amax)
+    return z, z[:, H:], (z[N:] if full else None)   # (z addresses its left half as it is)
+
+
+def _sage_dgrad(dz, wcat_t, dz_amax, w_amax, g, cfg: LayerConfig, dropadd: bool, gskip, img):
+    """dx = dz [W_l;W_r] plus the skip gradient: drop(g) added in the GEMM's epilogue (dropadd), or
+    accumulated onto the gskip the row pass wrote. wcat_t = [W_l;W_r]^T, so that the GEMM reads its
+    B operand K-contiguous; img: the layer's WPrep with a pre-split image of it, or None."""
+    N, H = dz.size(0), wcat_t.size(0)
+    pre = (img is not None and (dropadd or gskip is None)
+           and _lib.query("bgnn_gemm_w_tile", N, H, 2 * H) == img.bn_d)
+    if pre:
+        return _gemm_w(dz, img.img_d, img.bn_d, H, dz_amax, w_amax, g if dropadd else None, H,
+                       cfg.p if dropadd else 0.0, cfg.seed if dropadd else 0, timer="gemm_dgrad")
+    if dropadd:
+        return _gemm_dropadd(dz, wcat_t, dz_amax, w_amax, g, cfg.p, cfg.seed, timer="gemm_dgrad")
+    with _timed("gemm_dgrad"):
+        return gemm(dz, wcat_t, trans_a=False, trans_b=True, out=gskip, beta=1.0, a_amax=dz_amax, b_amax=w_amax,
+                    bf16=cfg.bf16)
+
+
 class SageLayerFn(torch.autograd.Function):
     """Outputs (x_next, max|x_next|): the second output (non-differentiable) is the f16x3 GEMM
     operand scale of the next layer, folded in by bgnn_sage_apply at no extra pass.
+    wprep: the layer's WPrep (prepare_weights) or None.
     pool (a SegmentIndex, the batch vector's segments): a third output, the mean pool of x_next
     per segment (global_mean_pool, Models/BuckGNN.py:246-249; the same segment kernel as
     bgnn.ops.segment_reduce). Its gradient reaches the backward row passes as the pooled
@@ -764,125 +997,40 @@ class SageLayerFn(torch.autograd.Function):
         dev = x_prev.device
         x_prev = x_prev.contiguous()
         H = w_l.size(0)
-        N = x_prev.size(0)
-        # [W_l;W_r] [2H, H] and its transpose (dgrad operand): from prepare_weights (all layers in
-        # a few launches; the amax slot then already holds max|W|) or built here
-        if isinstance(wprep, WPrep):
-            wcat, wcat_t_pre, img_f, img_d = wprep.wcat, wprep.wcat_t, wprep, wprep
-        elif wprep is not None:
-            (wcat, wcat_t_pre), img_f, img_d = wprep, None, None
-        else:
-            wcat, wcat_t_pre, img_f, img_d = torch.cat([w_l, w_r], 0).contiguous(), None, None, None
-        img_f = img_f if (img_f is not None and img_f.img_f is not None) else None
-        img_d = img_d if (img_d is not None and img_d.img_d is not None) else None
+        folded = w_in is not None
+        if folded and cfg.skip:
+            raise ValueError("sage_layer: a folded input transform needs a layer without skip")
         # operand maxima: [0] = max|W|, [1] = max|x_next| (this layer's output), [2] = max|dz|
         # (zeroed; the layer loop passes one slice of a single per-step fill)
         if amax is None:
             amax = torch.zeros(3, dtype=torch.float32, device=dev)
         w_amax, next_amax, dz_amax = amax[0:1], amax[1:2], amax[2:3]
-        folded = w_in is not None
+        # [W_l;W_r] [2H, H]: from prepare_weights (all layers in a few launches; the amax slot then
+        # already holds max|W|) or built here. A folded layer (K = K_in) transforms by Wf instead.
+        wcat = wprep.wcat if wprep is not None else torch.cat([w_l, w_r], 0).contiguous()
+        wmat, bf, wf_t = wcat, None, None
         if folded:
-            # the encoder's last Linear folded into this layer's transform (x_prev = its input h):
-            # x = h W_in^T + b_in never materialised; z = x [W_l;W_r]^T = h Wf^T + bf with
-            # Wf = [W_l;W_r] W_in [2H, K_in], bf = [W_l;W_r] b_in
-            if cfg.skip:
-                raise ValueError("sage_layer: a folded input transform needs a layer without skip")
-            wf_t = None
-            fold_native = not FOLD_WEIGHTS_TORCH and _fold_native_ok(cfg.famax, wcat, w_in, b_in)
-            if FOLD_WEIGHTS_TORCH:
-                wf = torch.mm(wcat, w_in)
-                bf = torch.mv(wcat, b_in)
-            elif fold_native:
-                K_in = w_in.size(1)
-                wf = torch.empty(2 * H, K_in, dtype=torch.float32, device=dev)
-                bf = torch.empty(2 * H, dtype=torch.float32, device=dev)
-                wf_t = torch.empty(K_in, 2 * H, dtype=torch.float32, device=dev) if DGRAD_WT else None
-                _lib.call("bgnn_fold_weights_fwd", H, K_in, wcat.data_ptr(), wcat.stride(0), w_in.data_ptr(),
-                          w_in.stride(0), b_in.data_ptr(), cfg.famax.data_ptr(), wf.data_ptr(), K_in, bf.data_ptr(),
-                          _ptr(wf_t), 2 * H, w_amax.data_ptr(), _stream())
-            else:
-                fs = cfg.famax
-                fa = (fs[0:1], fs[1:2], fs[2:3]) if fs is not None else (None, None, None)
-                if fs is not None:   # the same maxima the GEMMs would compute, without their fills
-                    absmax(wcat, fa[0], accumulate=True)
-                    absmax(w_in, fa[1], accumulate=True)
-                    absmax(b_in.view(1, -1), fa[2], accumulate=True)
-                wf = gemm(wcat, w_in.contiguous(), trans_a=False, trans_b=False, a_amax=fa[0], b_amax=fa[1])
-                # (bgnn GEMM, not torch.mv: rocBLAS's GEMV moved the BN-amplified gradients of the
-                # Shared variant 50x further from fp64, tests/test_gpu_fold.py)
-                bf = gemm(wcat, b_in.contiguous().view(H, 1), trans_a=False, trans_b=False, a_amax=fa[0],
-                          b_amax=fa[2]).view(-1)
-            if not fold_native:   # (the native launch folds max|Wf| in itself)
-                absmax(wf, w_amax, accumulate=True)
-            wmat = wf
-        else:
-            if wprep is None and not cfg.bf16:
-                absmax(wcat, w_amax, accumulate=True)
-            wmat, bf = wcat, None
+            wmat, bf, wf_t = _fold_fwd(wcat, w_in, b_in, cfg.famax, w_amax)
+        elif wprep is None and not cfg.bf16:
+            absmax(wcat, w_amax, accumulate=True)
         if x_amax is None:   # (the bf16 products take no operand scale: a placeholder for the saved list)
             x_amax = torch.empty(0, dtype=torch.float32, device=dev) if cfg.bf16 else absmax(x_prev)
-        planes = Z_PLANES and H % PLANE_TILE == 0 and not folded and not cfg.bf16
-        # range rows (RangeRows): x_prev is the head of an [N + R, H] buffer whose last R rows are the
-        # range sums of x_prev; the GEMM runs on all N + R rows and z_l's extra rows are the range
-        # rows' aggregates
-        rng = cfg.rng
-        x_full = rng.x_full if (rng is not None and rng.x_full is not None and not folded and not planes) else None
-        if x_full is not None and x_full.data_ptr() != x_prev.data_ptr():
-            raise RuntimeError("sage_layer: RangeRows.x_full must start at x_prev")
-        xa, a_amax_g = (x_full, rng.x_amax) if x_full is not None else (x_prev, x_amax)
-        M = xa.size(0)
-        # (the folded layer's transform has K = K_in, not H: timed under its own name so the
-        # bench's flops per launch are right for every launch it averages)
-        with _timed("gemm_fwd_fold" if folded else "gemm_fwd"):
-            if cfg.bf16:   # operands rounded to bf16 in-tile, z [N, 2H] stored bf16 (bgnn_gemm_bf16 storage 4)
-                z = gemm_bf16(x_prev, wmat, trans_a=False, trans_b=True, out_bf16=True)
-                zl = zr = None
-            elif planes:   # z = [z_l ; z_r] as two dense [N, H] planes
-                z = torch.empty(2, N, H, dtype=torch.float32, device=dev)
-                gemm(x_prev, wmat, trans_a=False, trans_b=True, out=Planes(z), a_amax=x_amax, b_amax=w_amax)
-                zl, zr, ldz = z[0], z[1], H
-            elif (img_f is not None and not folded
-                  and _lib.query("bgnn_gemm_w_tile", M, 2 * H, H) == img_f.bn_f):   # pre-split [W_l;W_r]
-                z = torch.empty(M, 2 * H, dtype=torch.float32, device=dev)
-                _lib.call("bgnn_gemm_f32_w", M, 2 * H, H, xa.data_ptr(), xa.stride(0), img_f.img_f.data_ptr(),
-                          img_f.bn_f, z.data_ptr(), 2 * H, None, 0, a_amax_g.data_ptr(), w_amax.data_ptr(), None, None,
-                          0, 0.0, 0, _stream())
-                zl, zr, ldz = z, z[:, H:], 2 * H
-            else:        # interleaved [M, 2H]
-                z = gemm(xa, wmat, trans_a=False, trans_b=True, bias=bf, a_amax=a_amax_g, b_amax=w_amax)
-                zl, zr, ldz = z, z[:, H:], 2 * H
-        hagg = z[N:] if x_full is not None else None
-        o = torch.empty(N, H, dtype=torch.float32, device=dev)
-        nrm = torch.empty(N, dtype=torch.float32, device=dev)
-        slots = _lib.query("bgnn_sage_fwd_bf16_slots" if cfg.bf16 else "bgnn_sage_fwd_slots", graph.fwd.ref())
-        bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)
-        part = (torch.empty(graph.fwd.plan.n_chunks * H, dtype=torch.float32, device=dev)
-                if graph.fwd.plan.n_chunks else None)
-        s = _stream()
-        with _timed("sage_fwd"):
-            if cfg.bf16:   # (batch statistics only where _glue_fwd reads them)
-                _lib.call("bgnn_sage_fwd_bf16", graph.fwd.ref(), z.data_ptr(), z.stride(0), b_l.data_ptr(), H,
-                          cfg.reduce, o.data_ptr(), nrm.data_ptr(),
-                          bn_part.data_ptr() if (cfg.bn and cfg.training) else None, _ptr(part), s)
-            else:
-                _lib.call("bgnn_sage_fwd", graph.fwd.ref(), zl.data_ptr(), ldz, zr.data_ptr(), ldz, b_l.data_ptr(), H,
-                          cfg.reduce, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), _ptr(part), _ptr(hagg),
-                          2 * H if hagg is not None else 0, s)
-        del z, zl, zr, hagg
-        x_next, (scale, shift, mean, invstd), pooled = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
-                                                                 running_var, cfg, next_amax, graph, pool, need_x)
+        # transform, rows, glue
+        zl, zr, hagg = _sage_transform(x_prev, x_amax, wmat, bf, w_amax, cfg,
+                                       wprep if (wprep is not None and wprep.img_f is not None) else None, folded)
+        # (bf16: batch statistics only where _glue_fwd reads them)
+        o, nrm, bn_part, slots = _sage_rows_fwd(graph.fwd, zl, zr, b_l, H, cfg.reduce, cfg.bn and cfg.training, hagg,
+                                                timer="sage_fwd")
+        del zl, zr, hagg
+        x_next, coeffs, pooled = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean, running_var, cfg,
+                                           next_amax, graph, pool, need_x)
         ctx.graph = graph
         ctx.cfg = cfg
-        ctx.folded = folded
-        ctx.wcat_t = wcat_t_pre
-        ctx.img_d = img_d if not folded else None
+        ctx.wcat_t = wprep.wcat_t if wprep is not None else None
+        ctx.img_d = wprep if (wprep is not None and wprep.img_d is not None and not folded) else None
         ctx.set_materialize_grads(False)   # the amax output never gets a gradient: no zero fill for it
-        ctx.fold = (w_in, b_in, wf, wf_t) if folded else None
-        ctx.save_for_backward(x_prev, o, nrm, wcat, gamma if gamma is not None else torch.empty(0, device=dev),
-                              scale if scale is not None else torch.empty(0, device=dev),
-                              shift if shift is not None else torch.empty(0, device=dev),
-                              mean if mean is not None else torch.empty(0, device=dev),
-                              invstd if invstd is not None else torch.empty(0, device=dev),
+        ctx.fold = (w_in, b_in, wmat, wf_t) if folded else None
+        ctx.save_for_backward(x_prev, o, nrm, wcat, _saved(gamma, dev), *(_saved(c, dev) for c in coeffs),
                               x_amax, w_amax, dz_amax)
         ctx.mark_non_differentiable(next_amax)
         ctx.pool = pool
@@ -896,147 +1044,60 @@ class SageLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_amax, g_pool=None):
         cfg: LayerConfig = ctx.cfg
-        g_rows = None
-        if g_pool is not None:   # mean pool: segment gradient / count (bgnn.ops._SegmentReduce.backward)
-            seg = ctx.pool
-            # one launch with the bits of g_pool / seg.fwd.degree().clamp_min(1).to(float32).unsqueeze(1)
-            gpc = g_pool.contiguous()
-            gp = torch.empty_like(gpc)
-            _lib.call("bgnn_pool_grad_scale", gpc.data_ptr(), seg.fwd.rowptr.data_ptr(), gpc.size(0), gpc.size(1),
-                      gp.data_ptr(), _stream())
-            if g is None and not cfg.skip:
-                g, g_rows = gp, seg.index
-            else:
-                gb = gp.index_select(0, seg.index)
-                g = gb if g is None else g + gb
+        g, g_rows = _pool_grad(g, g_pool, ctx.pool, cfg.skip)
         if g is None:   # (materialize_grads off: the layer output did not reach the loss)
             return (None,) * 17
         x_prev, o, nrm, wcat, gamma, scale, shift, mean, invstd, x_amax, w_amax, dz_amax = ctx.saved_tensors
         graph: Graph = ctx.graph
+        folded = ctx.fold is not None
         g = g.contiguous()
         N, H = o.shape
-        b16 = cfg.bf16   # the N-row dgrad / wgrad on bf16 operands; the row passes and A^T stay f32
-        planes = DZ_PLANES and H % PLANE_TILE == 0 and not b16
         dev = o.device
-        s = _stream()
-        bn = cfg.bn
-        dgamma, dbeta, sum_g2, sum_g2xhat = _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg, g_rows)
-        if planes:   # dz = [dz_l ; dh] as two dense [N, H] planes
+        b16 = cfg.bf16   # the N-row dgrad / wgrad on bf16 operands; the row passes and A^T stay f32
+        # dz = [dz_l | dh] and what its layout allows: two dense [N, H] planes take the plain GEMMs
+        # only; interleaved f32 rows also the drop-add epilogue (skip layers: the dgrad adds drop(g)
+        # itself, so the row pass writes no [N, H] skip gradient), the range rows (RangeRows: the
+        # transposed range rows' dz_l rows summed by the row pass) and the pre-split weight image
+        # (the bf16 products have none of the three: their skip gradient takes the gskip route)
+        if DZ_PLANES and H % PLANE_TILE == 0 and not b16:
             dzt = torch.empty(2, N, H, dtype=torch.float32, device=dev)
-            dz, dzl, dh, lddz = Planes(dzt), dzt[0], dzt[1], H
+            dz, dzl, dh = Planes(dzt), dzt[0], dzt[1]
+            dropadd, ranges, img_d = False, False, None
         else:
             dz = torch.empty(N, 2 * H, dtype=torch.float32, device=dev)
-            dzl, dh, lddz = dz, dz[:, H:], 2 * H
-        # skip layers: the dgrad's epilogue adds drop(g) itself (bgnn_gemm_f32_dropadd), so
-        # bgnn_sage_bwd_rows does not write the [N, H] skip gradient
-        # (the bf16 products have no drop-add epilogue: their skip gradient takes the gskip route)
-        dropadd = (cfg.skip and DGRAD_DROPADD and GEMM_BACKEND == "hip" and DGRAD_WT and not planes and not b16
-                   and H % 4 == 0 and _lib.query("bgnn_get_tuning", 5) == 2)
+            dzl, dh = dz, dz[:, H:]   # (dz addresses its left half as it is)
+            dropadd = (cfg.skip and DGRAD_DROPADD and GEMM_BACKEND == "hip" and not b16 and H % 4 == 0
+                       and _lib.query("bgnn_get_tuning", 5) == 2)
+            ranges = cfg.rng is not None and cfg.rng.bwd and graph.bwd.ranges is not None
+            img_d = None if b16 else ctx.img_d
         gskip = torch.empty(N, H, dtype=torch.float32, device=dev) if (cfg.skip and not dropadd) else None
-        rs = _lib.query("bgnn_rows_slots", N)
-        part_db = torch.empty(rs, 2, H, dtype=torch.float32, device=dev)
-        # range rows (RangeRows): the transposed range rows' dz_l rows summed by this pass
-        bw = graph.bwd
-        rb = (cfg.rng is not None and cfg.rng.bwd and not planes and bw.ranges is not None)
-        rp = (torch.empty(_lib.query("bgnn_range_partial_bytes", N, H) // 4, dtype=torch.float32, device=dev)
-              if rb else None)
-        _lib.call("bgnn_sage_bwd_rows", g.data_ptr(), _ptr(g_rows), o.data_ptr(), nrm.data_ptr(),
-                  _ptr(scale) if bn else None, _ptr(shift) if bn else None,
-                  _ptr(gamma) if (bn and gamma.numel()) else None,
-                  _ptr(mean) if bn else None, _ptr(invstd) if bn else None, _ptr(sum_g2), _ptr(sum_g2xhat),
-                  float(cfg.p), cfg.seed, int(cfg.skip and not dropadd), N, H, dh.data_ptr(), lddz, _ptr(gskip),
-                  part_db.data_ptr(), dz_amax.data_ptr(), graph.fwd.rowptr.data_ptr() if ctx.folded else None,
-                  (2 if cfg.reduce == 1 else 1) if ctx.folded else 0, _ptr(bw.ranges) if rb else None,
-                  graph.fwd.rowptr.data_ptr() if (rb and cfg.reduce == 1) else None, _ptr(rp), s)
-        if rb:   # the super nodes' dz_l rows (and their max |.| into dz_amax)
-            _lib.call("bgnn_range_sums_finish", rp.data_ptr(), N, H, bw.ref(), 1, dzl.data_ptr(), lddz, None,
-                      dz_amax.data_ptr(), s)
-        db2 = torch.empty(2 if ctx.folded else 1, H, dtype=torch.float32, device=dev)
-        # sum of dh (db_l) into the last row; folded input transform: the column sums of dz_l = A^T dh
-        # into row 0, so that db2 viewed flat is [sum dz_l ; sum dh], the folded layer's dbf
-        _lib.call("bgnn_reduce_partials", part_db.data_ptr(), rs, H, db2[-1].data_ptr(),
-                  db2[0].data_ptr() if ctx.folded else None, 0, s)
-        db, db_zl = db2[-1], (db2[0] if ctx.folded else None)
-        # dz_l = A^T dh (transpose CSR; MEAN scales by the target's in-degree)
-        part = torch.empty(bw.plan.n_chunks * H, dtype=torch.float32, device=dev) if bw.plan.n_chunks else None
-        with _timed("spmm_bwd"):
-            _lib.call("bgnn_spmm_bwd", bw.ref(), graph.perm_t.data_ptr(), graph.fwd.rowptr.data_ptr(),
-                      dh.data_ptr(), lddz, H, cfg.reduce, dzl.data_ptr(), lddz, _ptr(part),
-                      dz_amax.data_ptr(), int(rb), s)
-        has_affine = bn and gamma.numel() > 0
-        if ctx.folded:
-            # x = h W_in^T + b_in folded in: dh = dz Wf; dWf = dz^T h; dbf = column sums of dz;
-            # then dWcat = dWf W_in^T + dbf b_in^T (= dz^T x), dW_in = Wcat^T dWf, db_in = Wcat^T dbf
+        # stats, rows, transpose aggregation dz_l = A^T dh (MEAN scales by the target's in-degree)
+        dgamma, dbeta, sum_g2, sum_g2xhat = _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg, g_rows)
+        db2 = _sage_rows_bwd(g, g_rows, o, nrm, gamma, (scale, shift, mean, invstd), (sum_g2, sum_g2xhat), cfg, dh,
+                             dz_amax, gskip, graph, folded, dzl if ranges else None)
+        spmm_bwd_into(graph.bwd, graph.perm_t, graph.fwd.rowptr, dh, cfg.reduce, dzl, dz_amax, heavy_done=ranges,
+                      timer=_timed("spmm_bwd"))
+        has_affine = cfg.bn and gamma.numel() > 0
+        dgamma, dbeta = (dgamma, dbeta) if has_affine else (None, None)
+        if folded:
+            # x = h W_in^T + b_in folded in: dh = dz Wf; dWf = dz^T h; dbf = column sums of dz (db2)
             w_in, b_in, wf, wf_t = ctx.fold
-            wf_t = (wf_t if wf_t is not None else wf.t().contiguous()) if DGRAD_WT else wf
             with _timed("gemm_dgrad_fold"):
-                dx = gemm(dz, wf_t, trans_a=False, trans_b=DGRAD_WT, a_amax=dz_amax, b_amax=w_amax)
-            fs = cfg.famax
-            fa = (fs[0:1], fs[1:2], fs[2:3], fs[3:4], fs[4:5]) if fs is not None else (None,) * 5
+                dx = gemm(dz, wf_t if wf_t is not None else wf.t().contiguous(), trans_a=False, trans_b=True,
+                          a_amax=dz_amax, b_amax=w_amax)
             with _timed("gemm_wgrad_fold"):
                 dwf = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax,
-                           c_amax=fa[3])                                                   # [2H, K_in]
-            dbf = db2.view(-1)                                                              # Σ dz_l ; Σ dh
-            fold_native = not FOLD_WEIGHTS_TORCH and _fold_native_ok(fs, wcat, w_in, b_in) and dwf.stride(1) == 1
-            if fs is not None and not fold_native:
-                absmax(db2, fa[4], accumulate=True)
-            if fold_native:   # (max|dbf| folded into fs[4] by the launch itself)
-                K_in = w_in.size(1)
-                dw = torch.empty(2 * H, H, dtype=torch.float32, device=dev)
-                dw_in = torch.empty(H, K_in, dtype=torch.float32, device=dev)
-                db_in = torch.empty(H, dtype=torch.float32, device=dev)
-                ws_bytes = _lib.query("bgnn_fold_weights_ws_bytes", H, K_in)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-                _lib.call("bgnn_fold_weights_bwd", H, K_in, dwf.data_ptr(), dwf.stride(0), dbf.data_ptr(),
-                          wcat.data_ptr(), wcat.stride(0), w_in.data_ptr(), w_in.stride(0), b_in.data_ptr(),
-                          fs.data_ptr(), dw.data_ptr(), H, dw_in.data_ptr(), K_in, db_in.data_ptr(), _ptr(ws),
-                          ws_bytes, s)
-            elif FOLD_WEIGHTS_TORCH:
-                dw = torch.addmm(torch.outer(dbf, b_in), dwf, w_in.t())                    # [2H, H]
-                dw_in = torch.mm(wcat.t(), dwf)                                            # [H, K_in]
-                db_in = torch.mv(wcat.t(), dbf)                                            # [H]
-            else:
-                dw = gemm(dwf, w_in.contiguous(), trans_a=False, trans_b=True, a_amax=fa[3],
-                          b_amax=fa[1])                                                    # [2H, H]
-                dw.add_(torch.outer(dbf, b_in))
-                dw_in = gemm(wcat, dwf, trans_a=True, trans_b=False, a_amax=fa[0], b_amax=fa[3])  # [H, K_in]
-                db_in = gemm(wcat, dbf.view(-1, 1), trans_a=True, trans_b=False, a_amax=fa[0],
-                             b_amax=fa[4]).view(-1)                                        # [H]
-            return (dx, None, dw[:H], db, dw[H:], dgamma if has_affine else None, dbeta if has_affine else None,
-                    None, None, None, None, None, dw_in, db_in, None, None, None)
-        # dx = dz · Wcat (+ skip gradient);  dWcat = dz^T · x_prev
-        # [W_l;W_r] transposed once (2 MB) so the dgrad reads its B operand K-contiguous
-        wcat_t = (ctx.wcat_t if ctx.wcat_t is not None else wcat.t().contiguous()) if DGRAD_WT else wcat
-        img_d = ctx.img_d if (not planes and DGRAD_WT and not b16) else None
-        if (img_d is not None and (dropadd or gskip is None)
-                and _lib.query("bgnn_gemm_w_tile", N, H, 2 * H) == img_d.bn_d):   # pre-split [W_l;W_r]^T
-            dx = torch.empty(N, H, dtype=torch.float32, device=dev)
-            with _timed("gemm_dgrad"):
-                _lib.call("bgnn_gemm_f32_w", N, H, 2 * H, dz.data_ptr(), lddz, img_d.img_d.data_ptr(), img_d.bn_d,
-                          dx.data_ptr(), H, None, 0, dz_amax.data_ptr(), w_amax.data_ptr(), None,
-                          g.data_ptr() if dropadd else None, H, float(cfg.p) if dropadd else 0.0,
-                          cfg.seed if dropadd else 0, s)
-        elif dropadd:
-            dx = torch.empty(N, H, dtype=torch.float32, device=dev)
-            M_, K_ = N, 2 * H
-            ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", M_, H, K_, 0, 1, 0)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-            with _timed("gemm_dgrad"):
-                _lib.call("bgnn_gemm_f32_dropadd", 0, 1, M_, H, K_, dz.data_ptr(), lddz, wcat_t.data_ptr(),
-                          wcat_t.stride(0), dx.data_ptr(), H, dz_amax.data_ptr(), w_amax.data_ptr(), g.data_ptr(),
-                          H, float(cfg.p), cfg.seed, _ptr(ws), ws_bytes, s)
-        elif gskip is not None:
-            with _timed("gemm_dgrad"):
-                dx = gemm(dz, wcat_t, trans_a=False, trans_b=DGRAD_WT, out=gskip, beta=1.0, a_amax=dz_amax,
-                          b_amax=w_amax, bf16=b16)
-        else:
-            with _timed("gemm_dgrad"):
-                dx = gemm(dz, wcat_t, trans_a=False, trans_b=DGRAD_WT, a_amax=dz_amax, b_amax=w_amax, bf16=b16)
+                           c_amax=None if cfg.famax is None else cfg.famax[3:4])           # [2H, K_in]
+            dw, dw_in, db_in = _fold_bwd(dwf, db2, wcat, w_in, b_in, cfg.famax)
+            return (dx, None, dw[:H], db2[-1], dw[H:], dgamma, dbeta, None, None, None, None, None, dw_in, db_in,
+                    None, None, None)
+        # dgrad dx = dz · Wcat (+ skip gradient), wgrad dWcat = dz^T · x_prev [2H, H]
+        wcat_t = ctx.wcat_t if ctx.wcat_t is not None else wcat.t().contiguous()
+        dx = _sage_dgrad(dz, wcat_t, dz_amax, w_amax, g, cfg, dropadd, gskip, img_d)
         with _timed("gemm_wgrad"):
-            dw = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax, bf16=b16)  # [2H, H]
-        dw_l, dw_r = dw[:H], dw[H:]
-        return (dx, None, dw_l, db, dw_r, dgamma if has_affine else None, dbeta if has_affine else None,
-                None, None, None, None, None, None, None, None, None, None)
+            dw = gemm(dz, x_prev, trans_a=True, trans_b=False, a_amax=dz_amax, b_amax=x_amax, bf16=b16)
+        return (dx, None, dw[:H], db2[-1], dw[H:], dgamma, dbeta, None, None, None, None, None, None, None, None,
+                None, None)
 
 
 def _max_transform(x, w_l, w_r, graph: Graph, x_amax, w_amax, name: str):
@@ -1063,17 +1124,8 @@ def _max_rows_fwd(y, b_l, H: int):
     over a CSR without entries (graph.empty_csr), i.e. the SAGE row epilogue alone (the same
     arithmetic as the fused sum / mean layers' epilogue)."""
     from .graph import empty_csr
-    N = y.size(0)
-    dev = y.device
-    csr = empty_csr(N, dev)
-    bias = b_l if b_l is not None else torch.zeros(H, dtype=torch.float32, device=dev)
-    o = torch.empty(N, H, dtype=torch.float32, device=dev)
-    nrm = torch.empty(N, dtype=torch.float32, device=dev)
-    slots = _lib.query("bgnn_sage_fwd_slots", csr.ref())
-    bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)
-    _lib.call("bgnn_sage_fwd", csr.ref(), y.data_ptr(), y.stride(0), y.data_ptr(), y.stride(0), bias.data_ptr(), H,
-              0, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), None, None, 0, _stream())
-    return o, nrm, bn_part, slots
+    bias = b_l if b_l is not None else torch.zeros(H, dtype=torch.float32, device=y.device)
+    return _sage_rows_fwd(empty_csr(y.size(0), y.device), y, y, bias, H, 0)
 
 
 def _max_transform_bf16(x, w_l, w_r, graph: Graph, name: str):
@@ -1107,29 +1159,28 @@ def _max_rows_fwd_bf16(y, b_l, H: int, bn_stats: bool):
     sums, only where _glue_fwd reads them)."""
     from .graph import identity_csr
     N = y.size(0)
-    dev = y.device
     if y.dtype != torch.bfloat16 or tuple(y.shape) != (N, 2 * H) or not y.is_contiguous():
         raise ValueError("_max_rows_fwd_bf16: y must be a contiguous [N, 2H] bfloat16 tensor")
-    csr = identity_csr(N, dev)
-    o = torch.empty(N, H, dtype=torch.float32, device=dev)
-    nrm = torch.empty(N, dtype=torch.float32, device=dev)
-    slots = _lib.query("bgnn_sage_fwd_bf16_slots", csr.ref())
-    bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)
-    _lib.call("bgnn_sage_fwd_bf16", csr.ref(), y.data_ptr(), 2 * H, _ptr(b_l), H, 0,
-              o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr() if bn_stats else None, None, _stream())
-    return o, nrm, bn_part, slots
+    return _sage_rows_fwd(identity_csr(N, y.device), y, None, b_l, H, 0, bn_stats)
+
+
+def _max_scatter(dagg, t, arg, graph: Graph):
+    """dx = A_max^T dagg + t (bgnn_spmm_bwd_max, f32: the gradient of each (target, column) goes to
+    its argmax edge's source, CSR-first on ties)."""
+    dx = torch.empty(dagg.size(0), dagg.size(1), dtype=torch.float32, device=dagg.device)
+    spmm_bwd_max_into(graph.bwd, graph.perm_t, graph.fwd.rowptr, dagg, arg, t, dx, timer=_timed("spmm_bwd"))
+    return dx
 
 
 def _max_backward_bf16(dh, wcat_t, a, arg, graph: Graph, gskip, need_dx: bool):
     """_max_backward with bf16 operands in the N-row products (f32 accumulation and results):
         [dagg | t] = dh [W_l | W_r]          one product; a skip layer takes two, dagg on its own and
                                              t accumulated into gskip = drop(g) (beta = 1)
-        dx = A_max^T dagg + t                bgnn_spmm_bwd_max, f32, on the f32 argmax
+        dx = A_max^T dagg + t                _max_scatter, on the f32 argmax
         [dW_l^T ; dW_r^T] = a^T dh           a = bf16 [agg | x], as the forward product read it
     wcat_t = [W_l ; W_r]^T ([C, 2H])."""
-    N, H = dh.shape
+    H = dh.size(1)
     C = a.size(1) // 2
-    dev = dh.device
     dx = None
     if need_dx:
         with _timed("gemm_dgrad"):
@@ -1140,13 +1191,7 @@ def _max_backward_bf16(dh, wcat_t, a, arg, graph: Graph, gskip, need_dx: bool):
             else:
                 dagg = gemm(dh, wcat_t[:, :H], trans_a=False, trans_b=True, bf16=True)
                 t = gemm(dh, wcat_t[:, H:], trans_a=False, trans_b=True, out=gskip, beta=1.0, bf16=True)
-        dx = torch.empty(N, C, dtype=torch.float32, device=dev)
-        bw = graph.bwd
-        part = torch.empty(bw.plan.n_chunks * C, dtype=torch.float32, device=dev) if bw.plan.n_chunks else None
-        with _timed("spmm_bwd"):
-            _lib.call("bgnn_spmm_bwd_max", bw.ref(), graph.perm_t.data_ptr(), graph.fwd.rowptr.data_ptr(), N,
-                      dagg.data_ptr(), dagg.stride(0), C, arg.data_ptr(), t.data_ptr(), t.stride(0),
-                      dx.data_ptr(), dx.stride(0), _ptr(part), None, _stream())
+        dx = _max_scatter(dagg, t, arg, graph)
     with _timed("gemm_wgrad"):
         dwt = gemm_bf16(a, dh, trans_a=True, trans_b=False)              # [2C, H]
     return dx, dwt[:C].t(), dwt[C:].t()
@@ -1155,14 +1200,13 @@ def _max_backward_bf16(dh, wcat_t, a, arg, graph: Graph, gskip, need_dx: bool):
 def _max_backward(dh, dz_amax, wcat_t, x, agg, arg, graph: Graph, x_amax, w_amax, addend_beta_src,
                   need_dx: bool, p: float = 0.0, seed: int = 0):
     """Backward of y = [agg | x] [W_l | W_r]^T with agg = max-aggregate(x), given dh = dL/dy:
-        dagg = dh W_l, then dx = A_max^T dagg + (dh W_r [+ drop(g)])   (bgnn_spmm_bwd_max: the
-             gradient of each (target, column) goes to its argmax edge's source, CSR-first on ties)
+        dagg = dh W_l, then dx = A_max^T dagg + (dh W_r [+ drop(g)])   (_max_scatter)
         dW_l = dh^T agg,  dW_r = dh^T x
     wcat_t = [W_l ; W_r]^T ([C, 2H]); addend_beta_src: the skip connection's incoming gradient g
     (added through its dropout mask in the dW_r product's epilogue) or None."""
     N, H = dh.shape
     C = x.size(1)
-    dev = dh.device
+    g = addend_beta_src
     dx = None
     hip16 = GEMM_BACKEND == "hip" and _lib.query("bgnn_get_tuning", 5) == 2
     if need_dx and MAX_MERGED and hip16 and C % 256 == 0:
@@ -1171,47 +1215,27 @@ def _max_backward(dh, dz_amax, wcat_t, x, agg, arg, graph: Graph, x_amax, w_amax
         # instead of two at N = C
         wkt = torch.cat([wcat_t[:, :H], wcat_t[:, H:]], 0)          # [W_l^T ; W_r^T]
         with _timed("gemm_dgrad"):
-            dt = torch.empty(N, 2 * C, dtype=torch.float32, device=dev)
-            if addend_beta_src is not None:
-                ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", N, 2 * C, H, 0, 1, 0)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+            if g is not None:
+                dt = torch.empty(N, 2 * C, dtype=torch.float32, device=dh.device)
+                ws, ws_bytes = gemm_workspace(N, 2 * C, H, 0, 1, 0, dh.device)
                 _lib.call("bgnn_gemm_f32_dropadd_cols", N, 2 * C, H, dh.data_ptr(), dh.stride(0), wkt.data_ptr(), H,
-                          dt.data_ptr(), 2 * C, dz_amax.data_ptr(), w_amax.data_ptr(), addend_beta_src.data_ptr(),
-                          addend_beta_src.stride(0), C, float(p), seed, _ptr(ws), ws_bytes, _stream())
+                          dt.data_ptr(), 2 * C, dz_amax.data_ptr(), w_amax.data_ptr(), g.data_ptr(), g.stride(0), C,
+                          float(p), seed, _ptr(ws), ws_bytes, _stream())
             else:
-                gemm(dh, wkt, trans_a=False, trans_b=True, out=dt, a_amax=dz_amax, b_amax=w_amax)
-        dagg, t = dt[:, :C], dt[:, C:]
-        dx = torch.empty(N, C, dtype=torch.float32, device=dev)
-        bw = graph.bwd
-        part = torch.empty(bw.plan.n_chunks * C, dtype=torch.float32, device=dev) if bw.plan.n_chunks else None
-        with _timed("spmm_bwd"):
-            _lib.call("bgnn_spmm_bwd_max", bw.ref(), graph.perm_t.data_ptr(), graph.fwd.rowptr.data_ptr(), N,
-                      dagg.data_ptr(), 2 * C, C, arg.data_ptr(), t.data_ptr(), 2 * C,
-                      dx.data_ptr(), dx.stride(0), _ptr(part), None, _stream())
-        del dt, dagg, t
+                dt = gemm(dh, wkt, trans_a=False, trans_b=True, a_amax=dz_amax, b_amax=w_amax)
+        dx = _max_scatter(dt[:, :C], dt[:, C:], arg, graph)
+        del dt
     elif need_dx:
         wl_t, wr_t = wcat_t[:, :H], wcat_t[:, H:]                    # W_l^T, W_r^T: [C, H], ld 2H
         with _timed("gemm_dgrad"):
             dagg = gemm(dh, wl_t, trans_a=False, trans_b=True, a_amax=dz_amax, b_amax=w_amax)
-            if addend_beta_src is not None and hip16:
-                t = torch.empty(N, wcat_t.size(0), dtype=torch.float32, device=dev)
-                ws_bytes = _lib.query("bgnn_gemm_ws_bytes_ex", N, t.size(1), H, 0, 1, 0)
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-                _lib.call("bgnn_gemm_f32_dropadd", 0, 1, N, t.size(1), H, dh.data_ptr(), dh.stride(0),
-                          wr_t.data_ptr(), wr_t.stride(0), t.data_ptr(), t.stride(0), dz_amax.data_ptr(),
-                          w_amax.data_ptr(), addend_beta_src.data_ptr(), addend_beta_src.stride(0), float(p), seed,
-                          _ptr(ws), ws_bytes, _stream())
+            if g is not None and hip16:
+                t = _gemm_dropadd(dh, wr_t, dz_amax, w_amax, g, p, seed)
             else:
                 t = gemm(dh, wr_t, trans_a=False, trans_b=True, a_amax=dz_amax, b_amax=w_amax)
-                if addend_beta_src is not None:   # (torch GEMM backend / other GEMM modes: an explicit add)
-                    t.add_(_dropped(addend_beta_src, p, seed))
-        dx = torch.empty(N, x.size(1), dtype=torch.float32, device=dev)
-        bw = graph.bwd
-        part = torch.empty(bw.plan.n_chunks * x.size(1), dtype=torch.float32, device=dev) if bw.plan.n_chunks else None
-        with _timed("spmm_bwd"):
-            _lib.call("bgnn_spmm_bwd_max", bw.ref(), graph.perm_t.data_ptr(), graph.fwd.rowptr.data_ptr(), N,
-                      dagg.data_ptr(), dagg.stride(0), x.size(1), arg.data_ptr(), t.data_ptr(), t.stride(0),
-                      dx.data_ptr(), dx.stride(0), _ptr(part), None, _stream())
+                if g is not None:   # (torch GEMM backend / other GEMM modes: an explicit add)
+                    t.add_(_dropped(g, p, seed))
+        dx = _max_scatter(dagg, t, arg, graph)
     with _timed("gemm_wgrad"):
         if (MAX_MERGED and GEMM_BACKEND == "hip" and C % 256 == 0 and agg.shape == x.shape
                 and agg.stride() == x.stride() and (x.data_ptr() - agg.data_ptr()) % 16 == 0):
@@ -1236,7 +1260,8 @@ def _dropped(g, p: float, seed: int):
 class SageMaxLayerFn(torch.autograd.Function):
     """The fused layer of GraphSage_maxAggr (Models/BuckGNN.py:165-180,459-471): SAGEConv(aggr='max',
     normalize=True) -> BatchNorm -> ReLU -> skip -> Dropout, aggregate-first (_max_transform), then
-    the same row epilogue and glue kernels as the sum / mean layers. Outputs (x_next, max|x_next|)."""
+    the same row epilogue and glue kernels as the sum / mean layers. Outputs (x_next, max|x_next|).
+    wprep: the layer's WPrep (prepare_weights) or None."""
 
     @staticmethod
     def forward(ctx, x_prev, x_amax, w_l, b_l, w_r, gamma, beta, running_mean, running_var, graph: Graph,
@@ -1248,12 +1273,12 @@ class SageMaxLayerFn(torch.autograd.Function):
             amax = torch.zeros(3, dtype=torch.float32, device=dev)
         w_amax, next_amax, dz_amax = amax[0:1], amax[1:2], amax[2:3]
         if wprep is not None:   # (prepare_weights has folded max|[W_l;W_r]| into the slot)
-            w0, w1 = (wprep.wcat, wprep.wcat_t) if isinstance(wprep, WPrep) else wprep
-            wcat_t = w1 if w1 is not None else w0.t().contiguous()
+            wcat_t = wprep.wcat_t
         else:
             wcat_t = torch.cat([w_l, w_r], 0).t().contiguous()
             if not cfg.bf16:
                 absmax(wcat_t, w_amax, accumulate=True)
+        # transform, rows, glue
         if cfg.bf16:
             # autocast's rounding points: the bf16 products take no operand scale (a placeholder for
             # the saved list); `agg` is a = bf16 [agg | x], which also stands in for x_prev in the
@@ -1261,26 +1286,22 @@ class SageMaxLayerFn(torch.autograd.Function):
             if x_amax is None:
                 x_amax = torch.empty(0, dtype=torch.float32, device=dev)
             y, agg, arg = _max_transform_bf16(x_prev, w_l, w_r, graph, "gemm_fwd_max")
-            with _timed("sage_fwd"):
-                o, nrm, bn_part, slots = _max_rows_fwd_bf16(y, b_l, H, cfg.bn and cfg.training)
         else:
             if x_amax is None:
                 x_amax = absmax(x_prev)
             y, agg, arg = _max_transform(x_prev, w_l, w_r, graph, x_amax, w_amax, "gemm_fwd_max")
-            with _timed("sage_fwd"):
-                o, nrm, bn_part, slots = _max_rows_fwd(y, b_l, H)
+        with _timed("sage_fwd"):
+            o, nrm, bn_part, slots = (_max_rows_fwd_bf16(y, b_l, H, cfg.bn and cfg.training) if cfg.bf16
+                                      else _max_rows_fwd(y, b_l, H))
         del y
-        x_next, (scale, shift, mean, invstd), _ = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean,
-                                                            running_var, cfg, next_amax)
+        x_next, coeffs, _ = _glue_fwd(o, bn_part, slots, x_prev, gamma, beta, running_mean, running_var, cfg,
+                                      next_amax)
         ctx.graph = graph
         ctx.cfg = cfg
         ctx.set_materialize_grads(False)
-        e = torch.empty(0, device=dev)
         # (bf16: a replaces both agg and x_prev in the products; the skip reads g, not x_prev)
-        ctx.save_for_backward(e if cfg.bf16 else x_prev, agg, arg, o, nrm, wcat_t, gamma if gamma is not None else e,
-                              scale if scale is not None else e, shift if shift is not None else e,
-                              mean if mean is not None else e, invstd if invstd is not None else e,
-                              x_amax, w_amax, dz_amax)
+        ctx.save_for_backward(_saved(None if cfg.bf16 else x_prev, dev), agg, arg, o, nrm, wcat_t, _saved(gamma, dev),
+                              *(_saved(c, dev) for c in coeffs), x_amax, w_amax, dz_amax)
         ctx.mark_non_differentiable(next_amax)
         return x_next, next_amax
 
@@ -1294,32 +1315,23 @@ class SageMaxLayerFn(torch.autograd.Function):
         g = g.contiguous()
         N, H = o.shape
         dev = o.device
-        s = _stream()
-        bn = cfg.bn
-        dgamma, dbeta, sum_g2, sum_g2xhat = _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg)
         dh = torch.empty(N, H, dtype=torch.float32, device=dev)
-        rs = _lib.query("bgnn_rows_slots", N)
-        part_db = torch.empty(rs, 2, H, dtype=torch.float32, device=dev)
         # bf16: the products have no drop-add epilogue, so a skip layer's drop(g) is written by the
         # row pass (gskip) and the dh W_r product accumulates into it
         need_dx = ctx.needs_input_grad[0]
         gskip = (torch.empty(N, H, dtype=torch.float32, device=dev) if (cfg.bf16 and cfg.skip and need_dx)
                  else None)
-        _lib.call("bgnn_sage_bwd_rows", g.data_ptr(), None, o.data_ptr(), nrm.data_ptr(),
-                  _ptr(scale) if bn else None, _ptr(shift) if bn else None,
-                  _ptr(gamma) if (bn and gamma.numel()) else None,
-                  _ptr(mean) if bn else None, _ptr(invstd) if bn else None, _ptr(sum_g2), _ptr(sum_g2xhat),
-                  float(cfg.p), cfg.seed, int(gskip is not None), N, H, dh.data_ptr(), H, _ptr(gskip),
-                  part_db.data_ptr(), dz_amax.data_ptr(), None, 0, None, None, None, s)
-        db = torch.empty(H, dtype=torch.float32, device=dev)
-        _lib.call("bgnn_reduce_partials", part_db.data_ptr(), rs, H, db.data_ptr(), None, 0, s)
+        # stats, rows, then dgrad + transpose aggregation + wgrad
+        dgamma, dbeta, sum_g2, sum_g2xhat = _glue_bwd_stats(g, o, scale, shift, mean, invstd, cfg)
+        db2 = _sage_rows_bwd(g, None, o, nrm, gamma, (scale, shift, mean, invstd), (sum_g2, sum_g2xhat), cfg, dh,
+                             dz_amax, gskip)
         if cfg.bf16:
             dx, dw_l, dw_r = _max_backward_bf16(dh, wcat_t, agg, arg, ctx.graph, gskip, need_dx)
         else:
             dx, dw_l, dw_r = _max_backward(dh, dz_amax, wcat_t, x_prev, agg, arg, ctx.graph, x_amax, w_amax,
                                            g if cfg.skip else None, need_dx, cfg.p, cfg.seed)
-        has_affine = bn and gamma.numel() > 0
-        return (dx, None, dw_l, db, dw_r, dgamma if has_affine else None, dbeta if has_affine else None,
+        has_affine = cfg.bn and gamma.numel() > 0
+        return (dx, None, dw_l, db2[-1], dw_r, dgamma if has_affine else None, dbeta if has_affine else None,
                 None, None, None, None, None, None)
 
 
@@ -1335,10 +1347,9 @@ def _weight_pack(pairs, L: int, H: int):
     p.data bump no version, so a reused pack could be stale. Refilling costs nothing measurable.)"""
     dev = pairs[0][0].device
     W = torch.empty(L, 2 * H, H, dtype=torch.float32, device=dev)
-    Wt = torch.empty(L, H, 2 * H, dtype=torch.float32, device=dev) if DGRAD_WT else None
+    Wt = torch.empty(L, H, 2 * H, dtype=torch.float32, device=dev)
     torch._foreach_copy_([W[i, k * H:(k + 1) * H] for i in range(L) for k in (0, 1)], [t for pr in pairs for t in pr])
-    if Wt is not None:
-        Wt.copy_(W.transpose(1, 2))
+    Wt.copy_(W.transpose(1, 2))
     return W, Wt
 
 
@@ -1368,13 +1379,25 @@ def _wsplit_run(W, i, j, amax_bufs, M):
     return img, bn
 
 
+def _runs(flags):
+    """(i, j) of every maximal run flags[i:j] of consecutive true values."""
+    i, L = 0, len(flags)
+    while i < L:
+        j = i
+        while j < L and flags[j]:
+            j += 1
+        if j > i:
+            yield i, j
+        i = j + 1
+
+
 def prepare_weights(pairs, amax_bufs: torch.Tensor, fill_amax, n_rows: int = 0):
     """[W_l;W_r] and its transpose for every layer of a loop in a few launches (one multi-tensor
-    copy into a fresh pack, one transpose, one max|W|
-    launch per run of layers that take it) instead of three launches per layer. pairs:
-    [(w_l, w_r)] per layer; amax_bufs: the loop's zeroed [L, 3] operand-max slots, whose slot 0
-    receives max|[W_l;W_r]| for the layers where fill_amax[i] (a folded layer scales by max|Wf|
-    instead). Returns [(wcat, wcat_t)] per layer (views of two [L, ...] buffers)."""
+    copy into a fresh pack, one transpose, one max|W| launch per run of layers that take it)
+    instead of three launches per layer. pairs: [(w_l, w_r)] per layer; amax_bufs: the loop's
+    zeroed [L, 3] operand-max slots, whose slot 0 receives max|[W_l;W_r]| for the layers where
+    fill_amax[i] (a folded layer scales by max|Wf| instead). n_rows > 0: also the pre-split images
+    for GEMMs of n_rows rows (WSPLIT). Returns a WPrep per layer (views of [L, ...] buffers)."""
     L = len(pairs)
     H = pairs[0][0].size(0)
     with torch.no_grad():   # operands only: the layers return the weight gradients themselves
@@ -1384,37 +1407,22 @@ def prepare_weights(pairs, amax_bufs: torch.Tensor, fill_amax, n_rows: int = 0):
             W, Wt = _weight_pack(pairs, L, H)
         else:
             W = torch.cat([t for pr in pairs for t in pr], 0).view(L, 2 * H, H)
-            Wt = W.transpose(1, 2).contiguous() if DGRAD_WT else None
+            Wt = W.transpose(1, 2).contiguous()
         # max|W| per layer with bgnn_absmax (torch's dim=(1, 2) max-reduction took 128 us here),
         # one launch per run of consecutive layers that take it (the folded first layer does not)
-        i = 0
-        while i < L:
-            if not fill_amax[i]:
-                i += 1
-                continue
-            j = i
-            while j < L and fill_amax[j]:
-                j += 1
-            if ABSMAX_ITEMS and amax_bufs.is_contiguous() and H % 4 == 0:
+        for i, j in _runs(fill_amax):
+            if amax_bufs.is_contiguous() and H % 4 == 0:
                 _lib.call("bgnn_absmax_items_f32", W[i].data_ptr(), j - i, 2 * H * H, 2 * H, H, H,
                           amax_bufs[i].data_ptr(), amax_bufs.stride(0), _stream())
             else:
                 for k in range(i, j):
                     absmax(W[k], amax_bufs[k, 0:1], accumulate=True)
-            i = j
-        out = [WPrep(W[i], Wt[i] if Wt is not None else None) for i in range(L)]
+        out = [WPrep(W[i], Wt[i]) for i in range(L)]
         # pre-split images (after the maxima they are scaled by): the layers that scale by
         # max|[W_l;W_r]| (not a folded layer, whose transform is a per-step weight product)
-        if (WSPLIT and n_rows > 0 and GEMM_BACKEND == "hip" and Wt is not None and not Z_PLANES and not DZ_PLANES
+        if (WSPLIT and n_rows > 0 and GEMM_BACKEND == "hip" and not Z_PLANES and not DZ_PLANES
                 and amax_bufs.is_contiguous() and _lib.query("bgnn_get_tuning", 5) == 2):
-            i = 0
-            while i < L:
-                if not fill_amax[i]:
-                    i += 1
-                    continue
-                j = i
-                while j < L and fill_amax[j]:
-                    j += 1
+            for i, j in _runs(fill_amax):
                 img_f, bn_f = _wsplit_run(W, i, j, amax_bufs, n_rows)
                 img_d, bn_d = _wsplit_run(Wt, i, j, amax_bufs, n_rows)
                 for k in range(i, j):
@@ -1423,7 +1431,6 @@ def prepare_weights(pairs, amax_bufs: torch.Tensor, fill_amax, n_rows: int = 0):
                         o.img_f, o.bn_f = img_f[k - i], bn_f
                     if img_d is not None:
                         o.img_d, o.bn_d = img_d[k - i], bn_d
-                i = j
     return out
 
 
@@ -1470,39 +1477,30 @@ def sage_layer(x_prev: torch.Tensor, w_l: torch.Tensor, b_l: torch.Tensor, w_r: 
     if bf16 and w_in is not None:
         raise ValueError("sage_layer: bf16 takes no folded input transform (w_in): the folded Linear would join "
                          "the layer's bf16 product")
-    if bn_module is not None:
-        use_batch_stats = training or not bn_module.track_running_stats
-        momentum = bn_module.momentum
-        if training and bn_module.track_running_stats:
+    bn = bn_module
+    stats, momentum, eps = training, 0.0, 0.0
+    if bn is not None:
+        # the BatchNorm statistics follow `training or not track_running_stats`; dropout follows
+        # `training` alone (LayerConfig dropout=)
+        stats = training or not bn.track_running_stats
+        momentum = bn.momentum
+        if training and bn.track_running_stats:
             if count_batch:
-                bn_module.num_batches_tracked.add_(1)
+                bn.num_batches_tracked.add_(1)
             if momentum is None:   # cumulative average (torch: 1 / num_batches_tracked after the increment;
                 # with count_batch=False the caller has already incremented the counter)
-                momentum = 1.0 / float(bn_module.num_batches_tracked.item())
-        cfg = LayerConfig(reduce, True, use_batch_stats, float(momentum or 0.0) if bn_module.track_running_stats
-                          else 0.0, float(bn_module.eps), skip, p, seed)
-        cfg.p = p if training else 0.0
-        cfg.famax = fold_amax if w_in is not None else None
-        cfg.rng = rng if (reduce != 2 and not bf16) else None
-        cfg.bf16 = bool(bf16)
-        if reduce == 2:
-            out = SageMaxLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, bn_module.weight, bn_module.bias,
-                                       bn_module.running_mean, bn_module.running_var, graph, cfg, amax_buf, wprep)
-        else:
-            out = SageLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, bn_module.weight, bn_module.bias,
-                                    bn_module.running_mean, bn_module.running_var, graph, cfg, amax_buf, w_in, b_in,
-                                    wprep, pool, need_x)
+                momentum = 1.0 / float(bn.num_batches_tracked.item())
+        momentum = float(momentum or 0.0) if bn.track_running_stats else 0.0
+        eps = float(bn.eps)
+    cfg = LayerConfig(reduce, bn is not None, stats, momentum, eps, skip, p, seed, dropout=training,
+                      famax=fold_amax if w_in is not None else None,
+                      rng=rng if (reduce != 2 and not bf16) else None, bf16=bool(bf16))
+    bn_args = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4
+    if reduce == 2:
+        out = SageMaxLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, *bn_args, graph, cfg, amax_buf, wprep)
     else:
-        cfg = LayerConfig(reduce, False, training, 0.0, 0.0, skip, p, seed)
-        cfg.famax = fold_amax if w_in is not None else None
-        cfg.rng = rng if (reduce != 2 and not bf16) else None
-        cfg.bf16 = bool(bf16)
-        if reduce == 2:
-            out = SageMaxLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, None, None, None, None, graph, cfg, amax_buf,
-                                       wprep)
-        else:
-            out = SageLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, None, None, None, None, graph, cfg, amax_buf,
-                                    w_in, b_in, wprep, pool, need_x)
+        out = SageLayerFn.apply(x_prev, x_amax, w_l, b_l, w_r, *bn_args, graph, cfg, amax_buf, w_in, b_in, wprep,
+                                pool, need_x)
     if pool is not None:
         return out if return_amax else (out[0], out[2])
     return out if return_amax else out[0]
@@ -1544,16 +1542,8 @@ class SageConvFn(torch.autograd.Function):
         with _timed("conv_gemm_fwd"):
             z = gemm(x, wcat, trans_a=False, trans_b=True, a_amax=x_amax, b_amax=w_amax)   # [N, 2H]
         bias = b_l if b_l is not None else torch.zeros(H, dtype=torch.float32, device=dev)
-        o = torch.empty(N, H, dtype=torch.float32, device=dev)
-        nrm = torch.empty(N, dtype=torch.float32, device=dev)
-        slots = _lib.query("bgnn_sage_fwd_slots", graph.fwd.ref())
-        bn_part = torch.empty(slots, 2, H, dtype=torch.float32, device=dev)   # (BN sums: unused here)
-        part = (torch.empty(graph.fwd.plan.n_chunks * H, dtype=torch.float32, device=dev)
-                if graph.fwd.plan.n_chunks else None)
-        with _timed("conv_sage_fwd"):
-            _lib.call("bgnn_sage_fwd", graph.fwd.ref(), z.data_ptr(), 2 * H, z[:, H:].data_ptr(), 2 * H,
-                      bias.data_ptr(), H, reduce, o.data_ptr(), nrm.data_ptr(), bn_part.data_ptr(), _ptr(part),
-                      None, 0, _stream())
+        # (the BN sums are unused here)
+        o, nrm, _, _ = _sage_rows_fwd(graph.fwd, z, z[:, H:], bias, H, reduce, timer="conv_sage_fwd")
         ctx.save_for_backward(x, o, nrm, wcat, x_amax, w_amax)
         return o
 
@@ -1577,18 +1567,14 @@ class SageConvFn(torch.autograd.Function):
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = torch.empty(H, dtype=torch.float32, device=dev)
-            _lib.call("bgnn_reduce_partials", part_db.data_ptr(), rs, H, db.data_ptr(), None, 0, s)
+            reduce_partials(part_db, rs, H, db)
         if mx:
             agg, arg = ctx.saved_tensors[6:]
             dx, dw_l, dw_r = _max_backward(dh, dz_amax, wcat.t().contiguous(), x, agg, arg, graph, x_amax, w_amax,
                                            None, ctx.needs_input_grad[0])
             return dx, dw_l, db, dw_r, None, None
-        bw = graph.bwd
-        part = torch.empty(bw.plan.n_chunks * H, dtype=torch.float32, device=dev) if bw.plan.n_chunks else None
-        with _timed("conv_spmm_bwd"):
-            _lib.call("bgnn_spmm_bwd", bw.ref(), graph.perm_t.data_ptr(), graph.fwd.rowptr.data_ptr(),
-                      dh.data_ptr(), 2 * H, H, ctx.reduce, dz.data_ptr(), 2 * H, _ptr(part),
-                      dz_amax.data_ptr(), 0, s)
+        spmm_bwd_into(graph.bwd, graph.perm_t, graph.fwd.rowptr, dh, ctx.reduce, dz, dz_amax,
+                      timer=_timed("conv_spmm_bwd"))
         dx = None
         if ctx.needs_input_grad[0]:
             with _timed("conv_gemm_dgrad"):
@@ -1611,19 +1597,32 @@ def sage_conv(x: torch.Tensor, w_l: torch.Tensor, b_l, w_r: torch.Tensor, graph:
 # ---------------------------------------------------------------------------
 # bf16 inference layer (BuckGNN.infer_bf16): eval mode only, no autograd.
 
-def infer_weights(conv) -> torch.Tensor:
-    """[W_l ; W_r] of a SAGEConv as one bf16 [2H, H] matrix (the B^T operand of the layer's
-    GEMM), built once per weight version and kept on the module: rebuilt when either weight is
-    written in place (`_version`) or replaced (storage / device)."""
+def _cached_weights(conv, attr: str, dim: int) -> torch.Tensor:
+    """cat([W_l, W_r], dim) of a SAGEConv as one contiguous bf16 matrix, built once per weight
+    version and kept on the module under `attr`: rebuilt when either weight is written in place
+    (`_version`) or replaced (storage / device)."""
     w_l, w_r = conv.lin_l.weight, conv.lin_r.weight
     key = (w_l._version, w_r._version, w_l.data_ptr(), w_r.data_ptr(), str(w_l.device))
-    hit = getattr(conv, "_bgnn_infer_wcat", None)
+    hit = getattr(conv, attr, None)
     if hit is not None and hit[0] == key:
         return hit[1]
     with torch.no_grad():
-        wcat = torch.cat([w_l.detach(), w_r.detach()], 0).to(torch.bfloat16).contiguous()
-    conv._bgnn_infer_wcat = (key, wcat)
+        wcat = torch.cat([w_l.detach(), w_r.detach()], dim).to(torch.bfloat16).contiguous()
+    setattr(conv, attr, (key, wcat))
     return wcat
+
+
+def _bf16_rows(t: torch.Tensor) -> torch.Tensor:
+    """t as bf16 rows with unit column stride and an 8-element-aligned row stride (an f32 t is
+    rounded once)."""
+    t = t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
+    return t.contiguous() if (t.stride(1) != 1 or t.stride(0) % 8) else t
+
+
+def infer_weights(conv) -> torch.Tensor:
+    """[W_l ; W_r] of a SAGEConv as one bf16 [2H, H] matrix (the B^T operand of the layer's
+    GEMM), cached per weight version on the module (_cached_weights)."""
+    return _cached_weights(conv, "_bgnn_infer_wcat", 0)
 
 
 def bn_eval_coeffs(bn):
@@ -1657,16 +1656,10 @@ def sage_infer_layer(x: torch.Tensor, w_cat: torch.Tensor, bias, bn_coeffs, grap
     if reduce not in (0, 1):
         raise ValueError("sage_infer_layer: reduce must be 0 (sum) or 1 (mean)")
     dev = x.device
-    xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
-    if xb.stride(1) != 1 or xb.stride(0) % 8:
-        xb = xb.contiguous()
+    xb = _bf16_rows(x)
     with _timed("infer_gemm"):
         z = gemm_bf16(xb, w_cat, trans_a=False, trans_b=True, out_bf16=True)
-    xp = None
-    if x_prev is not None:
-        xp = x_prev if x_prev.dtype == torch.bfloat16 else x_prev.to(torch.bfloat16)
-        if xp.stride(1) != 1 or xp.stride(0) % 8:
-            xp = xp.contiguous()
+    xp = _bf16_rows(x_prev) if x_prev is not None else None
     scale, shift = bn_coeffs if bn_coeffs is not None else (None, None)
     out = torch.empty(N, H, dtype=torch.float32 if out_f32 else torch.bfloat16, device=dev)
     n_chunks = graph.fwd.plan.n_chunks
@@ -1684,17 +1677,8 @@ def sage_infer_layer(x: torch.Tensor, w_cat: torch.Tensor, bias, bn_coeffs, grap
 
 def infer_weights_max(conv) -> torch.Tensor:
     """[W_l | W_r] of a SAGEConv as one bf16 [H, 2H] matrix (the B^T operand of the max layer's
-    GEMM over [agg | x]), cached per weight version on the module as infer_weights is, under an
-    attribute of its own."""
-    w_l, w_r = conv.lin_l.weight, conv.lin_r.weight
-    key = (w_l._version, w_r._version, w_l.data_ptr(), w_r.data_ptr(), str(w_l.device))
-    hit = getattr(conv, "_bgnn_infer_wcat_max", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    with torch.no_grad():
-        wcat = torch.cat([w_l.detach(), w_r.detach()], 1).to(torch.bfloat16).contiguous()
-    conv._bgnn_infer_wcat_max = (key, wcat)
-    return wcat
+    GEMM over [agg | x]), cached as infer_weights is, under an attribute of its own."""
+    return _cached_weights(conv, "_bgnn_infer_wcat_max", 1)
 
 
 @torch.no_grad()

@@ -225,6 +225,7 @@ class _BatchNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         from . import _lib
+        from .fused import reduce_partials
         from .graph import _stream
         x, coef, w = ctx.saved_tensors
         g = g.contiguous()
@@ -237,7 +238,7 @@ class _BatchNormFn(torch.autograd.Function):
         _lib.call("bgnn_bn_bwd_stats", g.data_ptr(), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), N, C,
                   part.data_ptr(), s)
         sums = torch.empty(2, C, dtype=torch.float32, device=dev)   # dbeta, dgamma
-        _lib.call("bgnn_reduce_partials", part.data_ptr(), slots, C, sums[0].data_ptr(), sums[1].data_ptr(), 0, s)
+        reduce_partials(part, slots, C, sums[0], sums[1])
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)

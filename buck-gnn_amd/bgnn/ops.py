@@ -14,6 +14,8 @@
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import _lib
@@ -65,18 +67,47 @@ def spmm_bwd(csr_t, perm_t, fwd_rowptr, g: torch.Tensor, reduce: int, arg, out_r
     g = g.contiguous()
     H = g.size(1)
     gx = torch.empty(out_rows, H, dtype=torch.float32, device=g.device)
-    part = _partial(csr_t, H, 0, g.device)
     if out_rows > 0 and H > 0:
         if reduce == 2:
-            _lib.call("bgnn_spmm_bwd_max", csr_t.ref(), perm_t.data_ptr(), fwd_rowptr.data_ptr(), g.size(0),
-                      g.data_ptr(), g.stride(0), H, arg.data_ptr(), None, 0, gx.data_ptr(), gx.stride(0),
-                      None if part is None else part.data_ptr(), None if amax is None else amax.data_ptr(), _stream())
+            spmm_bwd_max_into(csr_t, perm_t, fwd_rowptr, g, arg, None, gx, amax)
         else:
-            _lib.call("bgnn_spmm_bwd", csr_t.ref(), None if perm_t is None else perm_t.data_ptr(),
-                      None if fwd_rowptr is None else fwd_rowptr.data_ptr(), g.data_ptr(), g.stride(0), H, reduce,
-                      gx.data_ptr(), gx.stride(0), None if part is None else part.data_ptr(),
-                      None if amax is None else amax.data_ptr(), 0, _stream())
+            spmm_bwd_into(csr_t, perm_t, fwd_rowptr, g, reduce, gx, amax)
     return gx
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+_NO_TIMER = contextlib.nullcontext()
+
+
+def spmm_bwd_into(csr_t, perm_t, fwd_rowptr, g: torch.Tensor, reduce: int, out: torch.Tensor, amax=None,
+                  heavy_done: bool = False, timer=None) -> None:
+    """out = A^T g for sum / mean (bgnn_spmm_bwd; rows = sources, MEAN scales by the target's
+    in-degree from fwd_rowptr). g is [*, H] float32 with unit column stride and any row stride
+    (a half of an interleaved [dz_l | dh] is), out addresses such rows by its data pointer and row
+    stride; amax: device scalar that max|out| is folded into; heavy_done: the heavy rows of out
+    are already written (range rows); timer: a context manager entered around the launch alone."""
+    H = g.size(1)
+    part = _partial(csr_t, H, 0, g.device)
+    with timer or _NO_TIMER:
+        _lib.call("bgnn_spmm_bwd", csr_t.ref(), _ptr(perm_t), _ptr(fwd_rowptr), g.data_ptr(), g.stride(0), H, reduce,
+                  out.data_ptr(), out.stride(0), _ptr(part), _ptr(amax), int(heavy_done), _stream())
+
+
+def spmm_bwd_max_into(csr_t, perm_t, fwd_rowptr, g: torch.Tensor, arg: torch.Tensor, addend, out: torch.Tensor,
+                      amax=None, timer=None) -> None:
+    """out = A_max^T g (+ addend) (bgnn_spmm_bwd_max): each (target, column) gradient of g (one
+    row per target of the forward) goes to the source of the argmax edge recorded in `arg`;
+    addend ([rows of out, H] or None) is added row by row. Row strides and timer as in
+    spmm_bwd_into."""
+    H = g.size(1)
+    part = _partial(csr_t, H, 0, g.device)
+    with timer or _NO_TIMER:
+        _lib.call("bgnn_spmm_bwd_max", csr_t.ref(), perm_t.data_ptr(), fwd_rowptr.data_ptr(), g.size(0), g.data_ptr(),
+                  g.stride(0), H, arg.data_ptr(), _ptr(addend), addend.stride(0) if addend is not None else 0,
+                  out.data_ptr(), out.stride(0), _ptr(part), _ptr(amax), _stream())
 
 
 def max_arg_positions(csr, arg: torch.Tensor, rows: int, H: int) -> torch.Tensor:

@@ -17,6 +17,48 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(bgnn_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_signatures():
+    """name -> (ctypes restype, [ctypes argtypes]) of every bgnn_* function include/bgnn.h declares.
+    Const-ness and parameter names are dropped; `int` is the 32-bit int of the ABI; bgnn_csr_t* maps
+    to POINTER(CsrStruct), a `char*` (the error string) to c_char_p, every other pointer to c_void_p."""
+    from bgnn import _lib
+
+    scalars = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+               "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
+    pointers = {"bgnn_csr_t": ctypes.POINTER(_lib.CsrStruct), "char": ctypes.c_char_p}
+    pointers.update({t: ctypes.c_void_p for t in ("float", "int32_t", "int64_t", "uint8_t", "void")})
+
+    def ctype(decl: str, named: bool):
+        tok = [t for t in decl.replace("*", " * ").split() if t != "const"]
+        if "*" in tok:
+            assert tok.count("*") == 1 and tok.index("*") == 1, decl
+            return pointers[tok[0]]
+        assert len(tok) == (2 if named else 1), decl
+        return scalars[tok[0]]
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([^;{}()]*?)\b(bgnn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in out, name
+        args = [] if params.strip() == "void" else [ctype(p, True) for p in params.split(",")]
+        out[name] = (ctype(ret, False), args)
+    return out
+
+
+def test_ctypes_signatures_match_the_header():
+    """_lib.SIGNATURES pins every declared function type for type: the return type and each
+    argument type in order (a positional ctypes call with a wrong type or order hands the kernels
+    wrong pointers without any error). Needs neither the GPU nor the built library."""
+    from bgnn import _lib
+
+    decl = declared_signatures()
+    assert sorted(decl) == declared_symbols()
+    assert sorted(decl) == sorted(_lib.SIGNATURES)
+    for name, sig in decl.items():
+        assert _lib.SIGNATURES[name] == sig, name
+
+
 def test_header_declares_entry_points():
     syms = declared_symbols()
     for s in ("bgnn_graph_build", "bgnn_spmm_fwd", "bgnn_spmm_bwd", "bgnn_sage_fwd", "bgnn_gemm_f32"):
