@@ -16,7 +16,8 @@ from .store import GraphStore
 from .checkpoint import load_checkpoint, load_reference_checkpoint, save_checkpoint
 from .dataset import load_dataset_cache
 from .inference import evaluate
-from .train import EigenvalueScaler, GradAllReduce, RelativeErrorLoss, mape_error, train_step
+from .train import ColumnScaler, EigenvalueScaler, GradAllReduce, RelativeErrorLoss, mape_error, train_step
+from .fused import node_head
 from . import losses
 from .losses import (GraphMAELoss, GraphMaxComponentRelativeError, GraphMixedError, GraphMSELoss,
                      GraphRelativeError, stress_errors)
@@ -28,7 +29,7 @@ __all__ = [
     "install_pyg_shim", "uninstall_pyg_shim", "EigenvalueScaler", "GradAllReduce", "RelativeErrorLoss",
     "mape_error", "train_step", "load_library", "GraphStore", "load_checkpoint", "load_reference_checkpoint",
     "save_checkpoint", "load_dataset_cache", "evaluate", "losses", "GraphMAELoss", "GraphMaxComponentRelativeError", "GraphMixedError",
-    "GraphMSELoss", "GraphRelativeError", "stress_errors",
+    "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head",
 ]
 
 

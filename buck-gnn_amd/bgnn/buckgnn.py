@@ -27,7 +27,7 @@ from . import ea as ea_mod
 from .ea import GradSlot as EAGradSlot, graphnet_block, skip_dropout
 from . import _lib
 from . import fused as _fused
-from .fused import RangeRows, mlp, mlp_bf16, prepare_weights, sage_layer, small_mlp
+from .fused import RangeRows, mlp, mlp_bf16, node_head, prepare_weights, sage_layer, small_mlp
 from .graph import SegmentIndex, graph_for, _index_cache
 from .nn import SAGEConv, SAGPooling, global_mean_pool, scatter_mean
 from .ops import segment_reduce
@@ -274,6 +274,16 @@ class BuckGNN(nn.Module):
         hooked = bool(dec._forward_pre_hooks or dec._forward_hooks)
         out = small_mlp(dec, h) if (self.use_fused and not hooked) else None
         return dec(h) if out is None else out
+
+    def _decode_nodes(self, x: Tensor) -> Optional[Tensor]:
+        """The node-level decoder on all N rows through bgnn.fused.node_head (the bgnn_head2 tail
+        kernel, a bgnn GEMM in front at h >= 256) on the fused path from 1024 rows on (the fused
+        encoder's threshold); None where the torch modules run (hooks, few rows, other shapes)."""
+        dec = self.decoder
+        hooked = bool(dec._forward_pre_hooks or dec._forward_hooks)
+        if hooked or not self._fused_ok(x) or x.size(0) < 1024 or not isinstance(dec, nn.Sequential):
+            return None
+        return node_head(dec, x)
 
     def _fused_ok(self, x: Tensor) -> bool:
         # float32 activations only: the fused kernels read f32 rows, so a bf16 activation (the
@@ -558,7 +568,10 @@ class BuckGNN(nn.Module):
                 pooled = self.get_pooling_layer(x, edge_index, batch)
             return self._decode(pooled).squeeze(), batch
         if "static" in self.prediction_type or "mode_shape" in self.prediction_type:
+            out = self._decode_nodes(x)
             if "super" in self.pooling_layer:
+                if out is not None:   # (row-independent decoder: the filter moves [N, C], not [N, H])
+                    return out[is_real_node], real_node_batch
                 return self.decoder(x[is_real_node]), real_node_batch
-            return self.decoder(x), batch
+            return (self.decoder(x) if out is None else out), batch
         raise ValueError(f"Unknown prediction type: {self.prediction_type}")

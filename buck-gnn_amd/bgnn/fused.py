@@ -547,6 +547,74 @@ def small_mlp(seq: torch.nn.Sequential, x: torch.Tensor):
     return SmallMLPFn.apply(x, tuple(relus), *params)
 
 
+class _Head2Fn(torch.autograd.Function):
+    """y = ReLU(x W1^T + b1) W2^T + b2 on bgnn_head2_fwd (the node-level decoder's tail, one launch,
+    the hidden activation never stored); backward: dx and the four weight / bias gradients from
+    bgnn_head2_bwd, which recomputes the hidden layer from x (deterministic slot sums)."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2):
+        N, D0 = x.shape
+        D1, C = W1.size(0), W2.size(0)
+        y = torch.empty(N, C, dtype=torch.float32, device=x.device)
+        _lib.call("bgnn_head2_fwd", x.data_ptr(), N, D0, D1, C, W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
+                  b2.data_ptr(), y.data_ptr(), _stream())
+        ctx.save_for_backward(x, W1, b1, W2)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W1, b1, W2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        N, D0 = x.shape
+        D1, C = W1.size(0), W2.size(0)
+        dx = torch.empty_like(x)
+        dW1, db1, dW2 = torch.empty_like(W1), torch.empty_like(b1), torch.empty_like(W2)
+        db2 = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws_bytes = _lib.query("bgnn_head2_bwd_ws_bytes", N, D0, C)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=x.device)
+        _lib.call("bgnn_head2_bwd", x.data_ptr(), N, D0, D1, C, W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
+                  dy.data_ptr(), dx.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(),
+                  ws.data_ptr(), ws_bytes, _stream())
+        return dx, dW1, db1, dW2, db2
+
+
+# the node-level decoder (prediction_type static_disp / static_stress / mode_shape) through
+# bgnn_head2 (node_head) instead of the torch modules
+FUSED_NODE_HEAD = True
+
+
+def node_head(seq: torch.nn.Sequential, x: torch.Tensor):
+    """seq(x) for the node-level decoder: Linear(D0,64).ReLU.Linear(64,C) as one bgnn_head2 kernel
+    (h <= 128: the whole decoder), with a leading Linear.ReLU on the bgnn GEMM in front (h >= 256:
+    Linear(h,128).ReLU, bias and ReLU in the epilogue). None when seq is not of that form with f32
+    contiguous weights and biases, the shapes are not built (bgnn_head2_supported), or x is not a
+    float32 [N >= 1, in_features] GPU tensor."""
+    if not (FUSED_NODE_HEAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) > 0):
+        return None
+    mods = list(seq)
+    want = (torch.nn.Linear, torch.nn.ReLU) * (len(mods) // 2) + (torch.nn.Linear,)
+    if len(mods) not in (3, 5) or not all(type(m) is t for m, t in zip(mods, want)):
+        return None
+    lins = mods[0::2]
+    if not all(m.weight.dtype == torch.float32 and m.weight.is_cuda and m.weight.is_contiguous() and m.bias is not None
+               and m.bias.is_contiguous() for m in lins):
+        return None
+    if x.size(1) != lins[0].in_features or any(a.out_features != b.in_features for a, b in zip(lins, lins[1:])):
+        return None
+    l1, l2 = lins[-2:]
+    if not _lib.query("bgnn_head2_supported", l1.in_features, l1.out_features, l2.out_features):
+        return None
+    if len(lins) == 3:
+        if lins[0].in_features % 4:
+            return None
+        x = linear(x, lins[0].weight, lins[0].bias, relu=True)
+    x = x.contiguous()
+    if x.data_ptr() % 16:
+        return None
+    return _Head2Fn.apply(x, l1.weight, l1.bias, l2.weight, l2.bias)
+
+
 def _mlp2_prefix(mods, x: torch.Tensor) -> bool:
     """Whether mods starts with Linear . ReLU . Linear . ReLU that bgnn_mlp2 covers for x."""
     if not FUSED_MLP2 or len(mods) < 4 or x.requires_grad or x.dtype != torch.float32 or x.dim() != 2:

@@ -77,6 +77,74 @@ def _elem_seg(batch: Tensor, x: Tensor) -> Tensor:
 
 
 # --------------------------------------------------------------------------------------------
+# the three per-graph-mean losses as one HIP kernel (bgnn_graph_loss)
+
+# GraphRelativeError / GraphMAELoss / GraphMSELoss with a batch vector on bgnn_graph_loss: loss and
+# d loss / d pred in two launches, sums in a fixed order (bit-stable; index_add_ is atomic)
+FUSED_GRAPH_LOSS = True
+_MULT = 10000.0
+
+
+class _GraphLossFn(torch.autograd.Function):
+    """bgnn_graph_loss: the loss, with d loss / d pred computed in the same pass and kept for the
+    backward (one multiply). scale / center: optional per-column affine applied to pred and target
+    before the element term (the denormalisation of bgnn.train.ColumnScaler)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, seg, kind: int, eps: float, scale, center):
+        from . import _lib
+        from .graph import _ptr, _stream
+        shape = pred.shape
+        p = pred.contiguous()
+        t = target.contiguous()
+        N = p.size(0)
+        C = p.numel() // N
+        B = seg.num_rows
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p)
+        ws_bytes = _lib.query("bgnn_graph_loss_ws_bytes", N, C, B)
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=p.device)
+        _lib.call("bgnn_graph_loss", p.data_ptr(), t.data_ptr(), N, C, seg.fwd.rowptr.data_ptr(),
+                  seg.fwd.col.data_ptr(), B, int(kind), float(eps), _MULT, _ptr(scale), _ptr(center),
+                  loss.data_ptr(), dpred.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+        ctx.save_for_backward(dpred.view(shape))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return dpred * g, None, None, None, None, None, None
+
+
+def _segments(batch: Tensor):
+    from .graph import SegmentIndex, _index_cache
+
+    def build():
+        return SegmentIndex.build(batch, int(batch.max().item()) + 1)
+    return _index_cache.get(batch, ("batch",), build)
+
+
+def graph_loss(kind: int, eps: float, pred: Tensor, target: Tensor, batch: Optional[Tensor], scale=None,
+               center=None) -> Optional[Tensor]:
+    """The per-graph-mean loss `kind` (0 relative, 1 MAE, 2 squares) of pred * scale + center against
+    target * scale + center (scale / center: [C] float32 tensors or None) on bgnn_graph_loss, or
+    None when the call does not qualify: float32 GPU pred and target of one [N] or [N, C <= 8] shape,
+    a batch vector of N graph ids on the same device, no gradient wanted for target."""
+    if not (FUSED_GRAPH_LOSS and batch is not None and pred.is_cuda and pred.dtype == torch.float32
+            and target.dtype == torch.float32 and target.device == pred.device and pred.shape == target.shape
+            and pred.dim() in (1, 2) and pred.size(0) > 0 and batch.device == pred.device and batch.dim() == 1
+            and batch.numel() == pred.size(0) and not batch.is_floating_point() and not target.requires_grad):
+        return None
+    C = pred.size(1) if pred.dim() == 2 else 1
+    if not 1 <= C <= 8:
+        return None
+    for v in (scale, center):
+        if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.numel() == C and v.is_contiguous()):
+            return None
+    return _GraphLossFn.apply(pred, target, _segments(batch), kind, eps, scale, center)
+
+
+# --------------------------------------------------------------------------------------------
 # losses (Utils/Losses.py)
 
 class GraphRelativeError(nn.Module):
@@ -88,6 +156,9 @@ class GraphRelativeError(nn.Module):
         self.epsilon = epsilon
 
     def forward(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], x=None) -> Tensor:
+        out = graph_loss(0, self.epsilon, pred, target, batch)
+        if out is not None:
+            return out
         rel = torch.abs(pred - target) / (torch.abs(target) + self.epsilon)
         if batch is None:
             return torch.mean(rel)
@@ -127,6 +198,9 @@ class GraphMSELoss(nn.Module):
     def forward(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], x=None) -> Tensor:
         if batch is None:
             return torch.mean(torch.abs(pred - target) ** 2)
+        out = graph_loss(2, 0.0, pred, target, batch)
+        if out is not None:
+            return out
         d = torch.abs(pred ** 2 - target ** 2)
         return torch.mean(_seg_mean(d.reshape(-1), _elem_seg(batch, d), _num_graphs(batch))) * 10000
 
@@ -139,6 +213,9 @@ class GraphMAELoss(nn.Module):
         self.alpha = alpha
 
     def forward(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], x=None) -> Tensor:
+        out = graph_loss(1, 0.0, pred, target, batch)
+        if out is not None:
+            return out
         d = torch.abs(pred - target)
         if batch is None:
             return torch.mean(d)

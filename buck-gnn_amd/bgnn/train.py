@@ -4,7 +4,9 @@
 for buckling targets: forward, RelativeErrorLoss on denormalised eigenvalues
 (Utils/Losses.py:755-761, Dataset_Preparation/Normalizer.py:207-215), backward,
 Adam step (TRAIN_FINAL.py:190). The reference's per-step `.item()` host syncs
-(TRAIN_FINAL.py:263,298) are optional here (`sync_metrics`).
+(TRAIN_FINAL.py:263,298) are optional here (`sync_metrics`). Node-level models
+(prediction_type static_disp / static_stress / mode_shape) take `_train_step_nodes`:
+the per-graph losses on ColumnScaler-denormalised rows (TRAIN_FINAL.py:264-292).
 
 `GradAllReduce` is the one collective of the multi-GPU path: the
 mini-batch is split by whole mesh graphs (no edge cuts), each rank runs its own
@@ -100,6 +102,87 @@ class EigenvalueScaler:
 
     def denormalize_eigenvalue(self, v):
         return v * self.scale + self.center
+
+
+class ColumnScaler:
+    """EigenvalueScaler's sibling for the node-level targets: the per-column affine
+    (de)normalisation of DatasetNormalizer's displacement / stress scalers (Normalizer.py:295-312):
+    value * scale[c] + center[c] (RobustScaler center_ / scale_), columns along the last axis."""
+
+    def __init__(self, center, scale):
+        self.center = torch.as_tensor(center, dtype=torch.float32).reshape(-1).contiguous()
+        self.scale = torch.as_tensor(scale, dtype=torch.float32).reshape(-1).contiguous()
+        if self.center.numel() != self.scale.numel():
+            raise ValueError("ColumnScaler: center and scale differ in length")
+        self._on = {}
+
+    def _at(self, device):
+        """(scale, center) on `device` (copied once per device)."""
+        key = str(device)
+        if key not in self._on:
+            self._on[key] = (self.scale.to(device), self.center.to(device))
+        return self._on[key]
+
+    def normalize(self, v):
+        scale, center = self._at(v.device)
+        return (v - center) / scale
+
+    def denormalize(self, v):
+        scale, center = self._at(v.device)
+        return v * scale + center
+
+    # the reference's names for the two node-level targets
+    denormalize_displacement = denormalize
+    denormalize_gp_stresses = denormalize
+
+
+def _denormalize_nodes(normalizer, prediction_type: str, v):
+    """The reference's per-prediction-type denormalisation (TRAIN_FINAL.py:264-292): displacements
+    for static_disp, Gauss-point stresses for static_stress, nothing for the other types."""
+    if normalizer is None:
+        return v
+    if type(normalizer) is ColumnScaler:
+        return normalizer.denormalize(v)
+    if prediction_type == "static_disp":
+        return normalizer.denormalize_displacement(v)
+    if prediction_type == "static_stress":
+        return normalizer.denormalize_gp_stresses(v)
+    return v
+
+
+def _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics: bool):
+    """train_step for the node-level heads (prediction_type static_disp / static_stress /
+    mode_shape; TRAIN_FINAL.py:255-297): criterion(denorm(pred), denorm(y), adjusted batch, x).
+    With one of bgnn.losses' three per-graph-mean classes and a ColumnScaler (or no normalizer) the
+    denormalisation runs inside the loss kernel (losses.graph_loss)."""
+    from . import losses
+    prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
+    pred, out_batch = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)
+    ptype = model.prediction_type
+    y = batch.y.contiguous() if ptype == "static_stress" else batch.y
+    kind = {losses.GraphRelativeError: 0, losses.GraphMAELoss: 1, losses.GraphMSELoss: 2}.get(type(criterion))
+    loss = None
+    if kind is not None and (normalizer is None or type(normalizer) is ColumnScaler):
+        scale, center = normalizer._at(pred.device) if normalizer is not None else (None, None)
+        loss = losses.graph_loss(kind, getattr(criterion, "epsilon", 0.0), pred, y, out_batch, scale, center)
+    if loss is None:
+        if isinstance(criterion, (losses.GraphRelativeError, losses.GraphMAELoss, losses.GraphMSELoss,
+                                  losses.GraphMixedError, losses.GraphMaxComponentRelativeError)):
+            fx = None   # (the bgnn classes ignore x: no gather)
+        elif "super" in model.pooling_layer:
+            fx = batch.x[batch.x[:, -1] == 0]
+        else:
+            fx = batch.x
+        loss = criterion(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
+                         out_batch, fx)
+    optimizer.zero_grad(set_to_none=True)
+    loss.backward()
+    if allreduce is not None:
+        allreduce()
+    optimizer.step()
+    if sync_metrics:
+        return float(loss.item()), float(losses.mape_error(pred.detach(), y, ptype).item())
+    return loss.detach()
 
 
 class GradAllReduce:
@@ -284,6 +367,8 @@ class GradAllReduce:
 
 def train_step(model, batch, optimizer, criterion, normalizer=None, allreduce: Optional[GradAllReduce] = None,
                sync_metrics: bool = False):
+    if getattr(model, "prediction_type", "buckling") != "buckling":
+        return _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics)
     # graph + pooling structure for this batch, one host sync (cached per tensor)
     prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
     pred, _ = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)

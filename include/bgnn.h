@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 20
+#define BGNN_ABI_VERSION 21
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -935,6 +935,50 @@ int bgnn_small_linear_fwd(const float* x, int64_t B, int32_t K, const float* W, 
                           int32_t relu, float* y, void* stream);
 int bgnn_small_linear_bwd(const float* gy, const float* y, const float* x, int64_t B, int32_t K, const float* W,
                           int32_t N, float* dx, float* dW, float* db, void* stream);
+
+/* ------------------------------------------------------------------------
+ * ABI 21: the node-level decoder's tail (Models/BuckGNN.py:76-100 with prediction_type
+ * static_disp / static_stress / mode_shape; the whole decoder at h <= 128, its last two Linears at
+ * h >= 256): y = ReLU(x W1^T + b1) W2^T + b2 for x [N, D0], W1 [D1, D0], W2 [C, D1], y [N, C],
+ * row-major fp32, on the VALU with both weights in LDS; the hidden activation is never stored.
+ * bgnn_head2_supported: D0 64 or 128, D1 64, 1 <= C <= 8. b1 / b2 may be NULL (zeros).
+ * bgnn_head2_bwd: given dy = dL/dy, dx [N, D0] (the gradient continues into the layers before) and
+ * the weight / bias gradients (written, not accumulated); the hidden layer is recomputed from x;
+ * per-workgroup partials in ws, summed in a fixed order (no atomics: bit-identical run to run).
+ * x and dx 16-byte aligned; ws 16-byte aligned, bgnn_head2_bwd_ws_bytes(N, D0, C) bytes. N = 0:
+ * no launch (the backward zero-fills the weight gradients).
+ * bgnn_head2_geometry(0 / 1 / 2): rows per tile, the forward's and the backward's largest grid (a
+ * workgroup takes a second tile when N exceeds rows * grid).
+ * ---------------------------------------------------------------------- */
+int bgnn_head2_supported(int32_t D0, int32_t D1, int32_t C);
+int bgnn_head2_geometry(int32_t which);
+int bgnn_head2_fwd(const float* x, int64_t N, int32_t D0, int32_t D1, int32_t C, const float* W1,
+                   const float* b1, const float* W2, const float* b2, float* y, void* stream);
+size_t bgnn_head2_bwd_ws_bytes(int64_t N, int32_t D0, int32_t C);
+int bgnn_head2_bwd(const float* x, int64_t N, int32_t D0, int32_t D1, int32_t C, const float* W1,
+                   const float* b1, const float* W2, const float* dy, float* dx, float* dW1, float* db1,
+                   float* dW2, float* db2, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * ABI 21: the per-graph losses of the node-level heads (Utils/Losses.py:362-401, 445-507 with a
+ * batch vector), loss and gradient in one pass:
+ *   *loss = mult / B * sum_g 1 / (n_g C) * sum_{i in g, c} f(p', t'),
+ *   p' = pred[i, c] * scale[c] + center[c], t' likewise from target (scale / center NULL: identity;
+ *   Normalizer.py:298-312), kind 0: f = |p' - t'| / (|t'| + eps) (GraphRelativeError), 1: |p' - t'|
+ *   (GraphMAELoss), 2: |p'^2 - t'^2| (GraphMSELoss);
+ *   dpred[i, c] = d loss / d pred[i, c] (NULL: skipped), with sign(0) = sign(NaN) = 0 as torch's
+ *   abs backward.
+ * pred / target [N, C] row-major, 1 <= C <= 8; (rowptr [B + 1], col) the segment CSR of the batch
+ * vector (graph -> its rows, any row order; every row in exactly one graph). The element term in
+ * f32 with torch's roundings, sums in double in a fixed order, no atomics; a graph without rows
+ * gives NaN (0 / 0), as the torch code. One workgroup per (graph, segment-block of the graph's
+ * elements), their sums in ws, then a one-workgroup finish kernel. ws:
+ * bgnn_graph_loss_ws_bytes(N, C, B) bytes, 8-byte aligned.
+ * ---------------------------------------------------------------------- */
+size_t bgnn_graph_loss_ws_bytes(int64_t N, int32_t C, int64_t B);
+int bgnn_graph_loss(const float* pred, const float* target, int64_t N, int32_t C, const int32_t* rowptr,
+                    const int32_t* col, int64_t B, int32_t kind, float eps, float mult, const float* scale,
+                    const float* center, float* loss, float* dpred, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
