@@ -15,12 +15,12 @@ from .pyg_shim import install_pyg_shim, uninstall_pyg_shim
 from .store import GraphStore
 from .checkpoint import load_checkpoint, load_reference_checkpoint, save_checkpoint
 from .dataset import load_dataset_cache
-from .inference import evaluate
+from .inference import evaluate, evaluate_nodes
 from .train import ColumnScaler, EigenvalueScaler, GradAllReduce, RelativeErrorLoss, mape_error, train_step
 from .fused import node_head
 from . import losses
 from .losses import (GraphMAELoss, GraphMaxComponentRelativeError, GraphMixedError, GraphMSELoss,
-                     GraphRelativeError, stress_errors)
+                     GraphRelativeError, StressErrorMeter, graph_metrics, stress_errors)
 
 __all__ = [
     "BuckGNN", "GraphNetBlock", "MLPPooling", "Batch", "Data", "DataLoader", "Graph", "SegmentIndex",
@@ -30,6 +30,7 @@ __all__ = [
     "mape_error", "train_step", "load_library", "GraphStore", "load_checkpoint", "load_reference_checkpoint",
     "save_checkpoint", "load_dataset_cache", "evaluate", "losses", "GraphMAELoss", "GraphMaxComponentRelativeError", "GraphMixedError",
     "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head",
+    "evaluate_nodes", "StressErrorMeter", "graph_metrics",
 ]
 
 

@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # BGNN_LIBRARY: a measurement build of the same ABI (make -C buck-gnn_amd m16), for tools/ only
 LIB_PATH = os.environ.get("BGNN_LIBRARY") or os.path.join(_HERE, "_lib", "libbgnn.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _lock = threading.Lock()
 _lib = None
@@ -172,6 +172,9 @@ SIGNATURES = {
     "bgnn_graph_loss_ws_bytes": (c_sz, [c_i64, c_i32, c_i64]),
     "bgnn_graph_loss": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_i32, c_f32, c_f32, c_p, c_p, c_p, c_p,
                                 c_p, c_sz, c_p]),
+    "bgnn_graph_metrics_ws_bytes": (c_sz, [c_i64, c_i32, c_i64]),
+    "bgnn_graph_metrics": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_i32, c_f32, c_p, c_p, c_p, c_p, c_sz,
+                                   c_p]),
     "bgnn_gemm_f32_dropadd": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p,
                                       c_p, c_p, c_i64, c_f32, c_u64, c_p, c_sz, c_p]),
     "bgnn_gemm_f32_dropadd_cols": (c_i32, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p,

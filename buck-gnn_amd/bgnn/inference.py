@@ -6,6 +6,10 @@ and reports, on denormalised eigenvalues, the MAPE summed over graphs divided by
 number of graphs, and the smallest and largest per-graph APE, all in percent. `evaluate`
 does the same over any iterable of batches: host-collated `Batch`es, or
 `GraphStore.loader(...)` batches gathered on the GPU.
+
+INFERENCE.py:153-172,189-199 does the same for the static heads with stress_errors per batch,
+summed key by key and divided by the number of batches: `evaluate_nodes`, on a device-side
+bgnn.losses.StressErrorMeter (one read-back at the end).
 """
 from __future__ import annotations
 
@@ -14,7 +18,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from .graph import prepare
-from .train import EigenvalueScaler
+from .train import ColumnScaler, EigenvalueScaler, _denormalize_nodes
 
 
 @torch.no_grad()
@@ -59,3 +63,44 @@ def _evaluate(model, batches, normalizer, device) -> Dict[str, float]:
         preds.append(pred.detach())
     return {"mape": total / max(n, 1), "min_mape": lo if n else 0.0, "max_mape": hi, "graphs": n,
             "predictions": torch.cat(preds) if preds else None}
+
+
+@torch.no_grad()
+def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, threshold: Optional[float] = None,
+                   device=None) -> Dict[str, object]:
+    """The static heads' evaluation (INFERENCE.py:153-172,189-199; the validation loop of
+    TRAIN_FINAL.py:349-384): eval mode, no_grad, per batch the model's prediction and its returned
+    (super-node adjusted) batch vector, stress_errors of the denormalised values accumulated in a
+    StressErrorMeter (threshold None: the reference's, 1e-4 for static_disp and 0.2 for
+    static_stress), and criterion(denorm(pred), denorm(y), batch, None) when a criterion is given.
+    normalizer: a bgnn.ColumnScaler (folded into the metric kernel), a reference-style object with
+    denormalize_displacement / denormalize_gp_stresses, or None.
+    Returns {"metrics_per_graph": sums / graphs, "metrics_per_batch": sums / batches, "graphs",
+    "batches", "loss": the mean criterion value over batches or None}."""
+    from . import losses
+    ptype = getattr(model, "prediction_type", "buckling")
+    if ptype not in losses.METRIC_KEYS:
+        raise ValueError(f"evaluate_nodes: a {ptype!r} model has no stress_errors metrics (static_disp or "
+                         "static_stress); bgnn.evaluate covers buckling")
+    model.eval()
+    meter = losses.StressErrorMeter(ptype, threshold)
+    loss_sum = None
+    for batch in batches:
+        if device is not None:
+            batch = batch.to(device)
+        prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
+        pred, out_batch = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)
+        y = batch.y.contiguous() if ptype == "static_stress" else batch.y
+        if normalizer is None or type(normalizer) is ColumnScaler:
+            scale, center = normalizer._at(pred.device) if normalizer is not None else (None, None)
+            meter.update(pred, y, out_batch, scale, center)
+        else:
+            meter.update(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
+                         out_batch)
+        if criterion is not None:
+            v = criterion(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
+                          out_batch, None).detach().double()
+            loss_sum = v if loss_sum is None else loss_sum + v
+    graphs, n = meter.counts
+    return {"metrics_per_graph": meter.compute("graph"), "metrics_per_batch": meter.compute("batch"), "graphs": graphs,
+            "batches": n, "loss": float(loss_sum.item()) / n if loss_sum is not None else None}

@@ -18,6 +18,13 @@ Semantics kept from the reference, including its quirks:
 * `stress_errors` returns SUMS over graphs (its comment says means), and the `*_high` /
   `*_low` entries sum only over graphs that have such elements (0 when none has);
 * per-component maxima take the first index of the largest |target| (torch.argmax).
+
+`stress_errors` on float32 GPU tensors runs as one HIP entry point (`graph_metrics`,
+bgnn_graph_metrics: the whole per-graph table of `METRIC_KEYS[prediction_type]` in two launches,
+exact per-graph 0.9-quantiles by radix select, sums in double in a fixed order, bit-stable) and one
+read-back; `FUSED_STRESS_ERRORS = False`, CPU tensors, doubles and more than 8 columns run the torch
+segment ops. `StressErrorMeter` accumulates the same sums on the device over the batches of an
+epoch (bgnn.train_step's `metrics=`, bgnn.evaluate_nodes) and reads them back once.
 """
 from __future__ import annotations
 
@@ -285,14 +292,149 @@ def _region_metrics(abs_diff: Tensor, rel_diff: Tensor, target: Tensor, pred: Te
     return {k: torch.where(present, v, torch.zeros_like(v)) for k, v in out.items()}
 
 
+# the per-graph metric table as one HIP entry point (bgnn_graph_metrics)
+
+# stress_errors / StressErrorMeter on bgnn_graph_metrics where the call qualifies (graph_metrics)
+FUSED_STRESS_ERRORS = True
+_REGION = ("mape", "re", "rmse", "mae", "p90")
+_TAIL = tuple(k + "_high" for k in _REGION) + tuple(k + "_low" for k in _REGION) + (
+    "mape", "re", "rmse", "mae", "mse", "p90", "max_mae", "std_mae", "p90_abs")
+# the table's metric columns in order (include/bgnn.h), = the reference's keys for the type; two
+# more columns follow: the element counts of the high and of the low region
+METRIC_KEYS = {
+    "static_stress": tuple(f"max_{c}_{k}" for c in ("x", "y", "xy") for k in ("val", "mae", "rel")) + _TAIL,
+    "static_disp": tuple(f"max_{c}_{k}" for c in ("disp", "x", "y") for k in ("val", "mae", "rel")) + _TAIL,
+}
+GRAPH_METRICS_COLS = 30
+_N_KEYS = 28
+# the reference's thresholds per type (TRAIN_FINAL.py:271-292)
+DEFAULT_THRESHOLD = {"static_disp": 1e-4, "static_stress": 0.2}
+
+
+def graph_metrics(pred: Tensor, target: Tensor, batch: Optional[Tensor], prediction_type: str, threshold: float,
+                  scale=None, center=None) -> Optional[Tensor]:
+    """The per-graph metric table [B, GRAPH_METRICS_COLS] (float64, on the device; columns
+    METRIC_KEYS[prediction_type], then the high / low element counts) of pred * scale + center
+    against target * scale + center on bgnn_graph_metrics, or None when the call does not qualify:
+    graph_loss's conditions (float32 GPU pred and target of one [N, C <= 8] shape, a batch vector of
+    N graph ids on the same device) with C >= 3 for static_stress and C >= 2 for static_disp. A
+    graph id without rows gives a NaN row with zero counts. No host sync beyond the cached segment
+    index of the batch vector."""
+    if prediction_type not in METRIC_KEYS:
+        raise NotImplementedError(f"Error metrics not implemented for prediction type: {prediction_type}")
+    if not (batch is not None and pred.is_cuda and pred.dtype == torch.float32 and target.dtype == torch.float32
+            and target.device == pred.device and pred.shape == target.shape and pred.dim() == 2 and pred.size(0) > 0
+            and batch.device == pred.device and batch.dim() == 1 and batch.numel() == pred.size(0)
+            and not batch.is_floating_point()):
+        return None
+    C = pred.size(1)
+    mode = 0 if prediction_type == "static_stress" else 1
+    if not (3 if mode == 0 else 2) <= C <= 8 or pred.numel() >= 2 ** 31:
+        return None
+    for v in (scale, center):
+        if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.numel() == C and v.is_contiguous()):
+            return None
+    from . import _lib
+    from .graph import _ptr, _stream
+    p = pred.detach().contiguous()
+    t = target.detach().contiguous()
+    seg = _segments(batch)
+    N, B = p.size(0), seg.num_rows
+    out = torch.empty((B, GRAPH_METRICS_COLS), dtype=torch.float64, device=p.device)
+    ws_bytes = _lib.query("bgnn_graph_metrics_ws_bytes", N, C, B)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=p.device)
+    _lib.call("bgnn_graph_metrics", p.data_ptr(), t.data_ptr(), N, C, seg.fwd.rowptr.data_ptr(),
+              seg.fwd.col.data_ptr(), B, mode, float(threshold), _ptr(scale), _ptr(center), out.data_ptr(),
+              ws.data_ptr(), ws_bytes, _stream())
+    return out
+
+
+def _fused_table(pred, target, batch, prediction_type, threshold, scale=None, center=None):
+    return graph_metrics(pred, target, batch, prediction_type, threshold, scale, center) if FUSED_STRESS_ERRORS \
+        else None
+
+
+class StressErrorMeter:
+    """stress_errors over the batches of an epoch, accumulated on the device: the reference adds the
+    per-batch dicts key by key (TRAIN_FINAL.py:300-304) and divides by the number of graphs
+    (TRAIN_FINAL.py:319,384) or of batches (INFERENCE.py:190).
+    update() adds a batch's sums over graphs and its graph count with no host sync (the table of
+    bgnn_graph_metrics; inputs that kernel declines go through the torch stress_errors, which
+    syncs); compute() is the one read-back. state() is the accumulator itself, [30] float64:
+    the 28 sums in METRIC_KEYS order, the graph count, the update count (a caller may all-reduce it)."""
+
+    def __init__(self, prediction_type: str, threshold: Optional[float] = None):
+        if prediction_type not in METRIC_KEYS:
+            raise ValueError(f"StressErrorMeter: no error metrics for prediction type {prediction_type!r} "
+                             "(static_stress or static_disp)")
+        self.prediction_type = prediction_type
+        self.threshold = DEFAULT_THRESHOLD[prediction_type] if threshold is None else float(threshold)
+        self.keys = METRIC_KEYS[prediction_type]
+        self._acc: Optional[Tensor] = None
+
+    def _state_on(self, device) -> Tensor:
+        if self._acc is None:
+            self._acc = torch.zeros(_N_KEYS + 2, dtype=torch.float64, device=device)
+        return self._acc
+
+    def update(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], scale=None, center=None) -> None:
+        """Add one batch. scale / center: the ColumnScaler's per-column affine ([C] float32 on the
+        device), applied to pred and target before the metrics (None: the values as they are)."""
+        acc = self._state_on(pred.device)
+        table = _fused_table(pred, target, batch, self.prediction_type, self.threshold, scale, center)
+        if table is not None:
+            acc[:_N_KEYS] += table[:, :_N_KEYS].sum(0)
+            acc[_N_KEYS] += table.size(0)
+        else:
+            p, t = pred.detach(), target
+            if scale is not None:
+                p, t = p * scale, t * scale
+            if center is not None:
+                p, t = p + center, t + center
+            d = stress_errors(p, t, batch, self.prediction_type, self.threshold)
+            acc[:_N_KEYS] += torch.tensor([d[k] for k in self.keys], dtype=torch.float64).to(acc.device)
+            acc[_N_KEYS] += _num_graphs(batch) if batch is not None else 1
+        acc[_N_KEYS + 1] += 1
+
+    def state(self) -> Optional[Tensor]:
+        return self._acc
+
+    def reset(self) -> None:
+        if self._acc is not None:
+            self._acc.zero_()
+
+    @property
+    def counts(self):
+        """(graphs, updates) so far (a host read)."""
+        if self._acc is None:
+            return 0, 0
+        g, u = self._acc[_N_KEYS:].tolist()
+        return int(g), int(u)
+
+    def compute(self, per: str = "graph") -> Dict[str, float]:
+        """The accumulated sums divided by the number of graphs (per="graph") or of updates
+        (per="batch"); NaN before the first update."""
+        if per not in ("graph", "batch"):
+            raise ValueError("StressErrorMeter.compute: per must be 'graph' or 'batch'")
+        if self._acc is None:
+            return {k: float("nan") for k in self.keys}
+        vals = self._acc.tolist()
+        den = vals[_N_KEYS] if per == "graph" else vals[_N_KEYS + 1]
+        return {k: (v / den if den else float("nan")) for k, v in zip(self.keys, vals)}
+
+
 def stress_errors(predictions: Tensor, targets: Tensor, batch: Optional[Tensor] = None,
                   prediction_type: str = "static_stress", threshold: float = 0.1) -> Dict[str, float]:
     """stress_errors (Dataset_Preparation/Metrics.py:25-191): per-graph error metrics of the
-    static stress ([N, 3]: x, y, xy) or displacement ([N, >= 2]) heads, summed over graphs."""
+    static stress ([N, 3]: x, y, xy) or displacement ([N, >= 2]) heads, summed over graphs.
+    float32 GPU tensors of at most 8 columns: bgnn_graph_metrics and one read-back of the sums."""
     if prediction_type not in ("static_stress", "static_disp"):
         raise NotImplementedError(f"Error metrics not implemented for prediction type: {prediction_type}")
     if batch is None:
         batch = torch.zeros(len(predictions), dtype=torch.long, device=predictions.device)
+    table = _fused_table(predictions, targets, batch, prediction_type, threshold)
+    if table is not None:
+        return dict(zip(METRIC_KEYS[prediction_type], table[:, :_N_KEYS].sum(0).tolist()))
     n = _num_graphs(batch)
     p, t = predictions, targets
     abs_diff = torch.abs(t - p)

@@ -150,11 +150,13 @@ def _denormalize_nodes(normalizer, prediction_type: str, v):
     return v
 
 
-def _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics: bool):
+def _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics: bool, metrics=None):
     """train_step for the node-level heads (prediction_type static_disp / static_stress /
     mode_shape; TRAIN_FINAL.py:255-297): criterion(denorm(pred), denorm(y), adjusted batch, x).
     With one of bgnn.losses' three per-graph-mean classes and a ColumnScaler (or no normalizer) the
-    denormalisation runs inside the loss kernel (losses.graph_loss)."""
+    denormalisation runs inside the loss kernel (losses.graph_loss). metrics: a
+    losses.StressErrorMeter that takes the step's detached prediction and the targets
+    (TRAIN_FINAL.py:271-292: stress_errors on the denormalised values, every step)."""
     from . import losses
     prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
     pred, out_batch = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)
@@ -180,6 +182,13 @@ def _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce,
     if allreduce is not None:
         allreduce()
     optimizer.step()
+    if metrics is not None:
+        if normalizer is None or type(normalizer) is ColumnScaler:
+            scale, center = normalizer._at(pred.device) if normalizer is not None else (None, None)
+            metrics.update(pred.detach(), y, out_batch, scale, center)
+        else:
+            metrics.update(_denormalize_nodes(normalizer, ptype, pred.detach()),
+                           _denormalize_nodes(normalizer, ptype, y), out_batch)
     if sync_metrics:
         return float(loss.item()), float(losses.mape_error(pred.detach(), y, ptype).item())
     return loss.detach()
@@ -366,9 +375,16 @@ class GradAllReduce:
 
 
 def train_step(model, batch, optimizer, criterion, normalizer=None, allreduce: Optional[GradAllReduce] = None,
-               sync_metrics: bool = False):
-    if getattr(model, "prediction_type", "buckling") != "buckling":
-        return _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics)
+               sync_metrics: bool = False, metrics=None):
+    """One training step. metrics: an optional bgnn.losses.StressErrorMeter for a static_disp /
+    static_stress model; it is updated on the device with the step's detached prediction and the
+    targets, denormalised as the loss sees them (no host sync). None changes nothing."""
+    ptype = getattr(model, "prediction_type", "buckling")
+    if metrics is not None and ptype != getattr(metrics, "prediction_type", None):
+        raise ValueError(f"train_step: a {getattr(metrics, 'prediction_type', None)!r} metrics meter with a "
+                         f"{ptype!r} model (the error metrics exist for static_disp and static_stress heads)")
+    if ptype != "buckling":
+        return _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics, metrics)
     # graph + pooling structure for this batch, one host sync (cached per tensor)
     prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
     pred, _ = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)

@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BGNN_ABI_VERSION 21
+#define BGNN_ABI_VERSION 22
 
 #define BGNN_OK 0
 #define BGNN_E_ARG 1001       /* invalid argument (shape, null pointer, size)    */
@@ -979,6 +979,47 @@ size_t bgnn_graph_loss_ws_bytes(int64_t N, int32_t C, int64_t B);
 int bgnn_graph_loss(const float* pred, const float* target, int64_t N, int32_t C, const int32_t* rowptr,
                     const int32_t* col, int64_t B, int32_t kind, float eps, float mult, const float* scale,
                     const float* center, float* loss, float* dpred, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * ABI 22: the per-graph error metrics of the static heads (Dataset_Preparation/Metrics.py:25-191,
+ * stress_errors) as one table out[B, BGNN_GRAPH_METRICS_COLS] of doubles, row g = graph g.
+ * pred / target [N, C] row-major, (rowptr [B + 1], col) the batch vector's segment CSR as for
+ * bgnn_graph_loss (any row order), 1 <= C <= 8 and N C < 2^31; scale / center [C] or NULL:
+ * p = pred * scale[c] + center[c], t likewise. With a = |t - p|, r = a / (|t| + 1e-8), all in f32
+ * with torch's roundings:
+ *   mode 0 (static_stress, C >= 3; columns 0..2 are x, y, xy): an element is "high" where
+ *     |t| >= threshold, else "low";
+ *   mode 1 (static_disp, C >= 2): a row is high where its magnitude m = sqrt(sum_c t_c^2) >= threshold
+ *     (squares and sums rounded in column order, the root correctly rounded), with all its C elements.
+ * Columns (mode 0 | mode 1), `*` = the first row (smallest row index) of the largest value:
+ *    0.. 2  max_x_val, max_x_mae, max_x_rel   | max_disp_val, max_disp_mae, max_disp_rel
+ *    3.. 5  max_y_val, max_y_mae, max_y_rel   | max_x_val, max_x_mae, max_x_rel
+ *    6.. 8  max_xy_val, max_xy_mae, max_xy_rel | max_y_val, max_y_mae, max_y_rel
+ *           (val = |t| at *, mae = a at *, rel = r at * x 100 in f32; max_disp_*: m at *, the norm of
+ *           the row's a, and their f32 ratio mae / (val + 1e-8) x 100)
+ *    9..13  mape_high, re_high, rmse_high, mae_high, p90_high   (over the high elements)
+ *   14..18  mape_low, re_low, rmse_low, mae_low, p90_low        (over the low elements)
+ *   19..24  mape, re, rmse, mae, mse, p90                       (over all n_g C elements)
+ *   25..27  max_mae, std_mae, p90_abs
+ *   28, 29  the number of high and of low elements
+ *   mape = 100 mean r, re = 100 sum a / sum |t|, rmse = sqrt(mean(t^2 - p^2)) (NaN where the mean is
+ *   negative), mae = mean a, mse = mean(t^2 - p^2), p90 = 100 x the 0.9-quantile of r, max_mae = max a,
+ *   std_mae = the unbiased standard deviation of a (two passes; one element: NaN), p90_abs = the
+ *   0.9-quantile of a. Quantiles as torch.quantile (linear): the rank 0.9f * (n - 1) in f32, the two
+ *   exact order statistics by radix select, lerp in f32; a NaN among the elements gives NaN.
+ * Sums in double in a fixed order, no floating-point atomics: bit-identical from run to run. A
+ * region without elements writes 0 in its five columns and in its count. A graph id without rows
+ * (undefined in the reference) gets NaN in columns 0..27 and 0 in 28, 29. Targets must be finite.
+ * One workgroup per graph for the sums, one per (graph, quantile) for the selects; no limit on a
+ * graph's size. out: B x BGNN_GRAPH_METRICS_COLS doubles, 8-byte aligned (a void* like every buffer
+ * of this header that is not float or integer). ws: bgnn_graph_metrics_ws_bytes(N, C, B) bytes,
+ * 8-byte aligned, non-NULL.
+ * ---------------------------------------------------------------------- */
+#define BGNN_GRAPH_METRICS_COLS 30
+size_t bgnn_graph_metrics_ws_bytes(int64_t N, int32_t C, int64_t B);
+int bgnn_graph_metrics(const float* pred, const float* target, int64_t N, int32_t C, const int32_t* rowptr,
+                       const int32_t* col, int64_t B, int32_t mode, float threshold, const float* scale,
+                       const float* center, void* out, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
