@@ -3,7 +3,7 @@
 // kernel reads (GatherArgs), the row-group walker (walk_groups), the per-row edge gather
 // (gather_edges), the heavy-chunk body (chunk_body), the 16-wave combine of f32 chunk partials
 // (combine_chunks) and the host side (argument checks, CSR fill, group eligibility, launch
-// sequence). A file supplies its argument struct (derived from GatherArgs), a policy, an epilogue
+// sequence; the grid, grid8, is seg_common.h's). A file supplies its argument struct (derived from GatherArgs), a policy, an epilogue
 // and thin __global__ wrappers.
 //
 // Mapping: a lane owns 8 consecutive columns (one 16-byte load of bf16), so a 512-column row is one
@@ -279,7 +279,7 @@ __device__ __forceinline__ void chunk_body(const GatherArgs& A, const P& pol, in
 // wave 0, whose lanes inside H then hold the row's sum in a; the other waves are done. Wave 0's loop
 // over the run sums is unrolled by 5, not fully: with all 15 steps' LDS reads in flight the block's
 // 128-VGPR budget (__launch_bounds__(1024)) overflowed into scratch in k_b16_combine.
-constexpr int kCombineWaves = 16;
+// (kCombineWaves: seg_common.h)
 __device__ __forceinline__ bool combine_chunks(const GatherArgs& A, int h, int cs, bool ok, float (&a)[8]) {
     constexpr int W = kCombineWaves;
     __shared__ __attribute__((aligned(16))) float red[W][512];
@@ -374,13 +374,6 @@ inline int check_aligned_and_fill(const char* name, const char* ops, const bgnn_
     A.partial = partial;
     *go = 1;
     return BGNN_OK;
-}
-
-inline int64_t grid8(int64_t waves_wanted, int64_t cap) {
-    int64_t blocks = (waves_wanted + 3) / 4;   // at most one row / group per wave
-    if (blocks > cap) blocks = cap;
-    blocks = (blocks + 7) / 8 * 8;
-    return blocks < 8 ? 8 : blocks;
 }
 
 // Whether the light rows can run on the CSR's row-group plan -- every light row's keys must fit

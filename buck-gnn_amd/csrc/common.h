@@ -95,6 +95,11 @@ void set_rows_nt(int on);
 int rows_nt();
 void set_rows_rev(int on);
 int rows_rev();
+// the aggregation kernels' knobs (spmm.hip; BGNN_TUNE_SEG_* / BGNN_TUNE_GROUP_BLOCKS, tuning.hip)
+struct SegTuning {
+    int kernel, grp_blocks, blocks, nt, u;
+};
+extern SegTuning g_seg;
 // bgnn_spmm_fwd's combine of the heavy rows' chunk partials [n_chunks, H] into out [n_rows, H]
 // (SUM / MEAN, float4 geometry: H % 4 == 0, 16-B aligned partial / out), launched alone (spmm.hip)
 int seg_combine_plain(const bgnn_csr_t* csr, int32_t H, int32_t reduce, float* partial, float* out, hipStream_t s);

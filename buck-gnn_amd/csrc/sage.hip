@@ -741,7 +741,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
         float* rd = rpart + (int64_t)lb * kRangeSlots * H;
         for (int c = threadIdx.x; c < kRangeSlots * H; c += 256) {
             const int q = c / H, cc = c % H;
-            rd[c] = (red[0][q][cc] + red[1][q][cc]) + (red[2][q][cc] + red[3][q][cc]);
+            rd[c] = wave_tree(red, q, cc);
         }
         __syncthreads();
     }
@@ -756,8 +756,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     __syncthreads();
     float* dst = part + (int64_t)lb * 2 * H;
     for (int c = threadIdx.x; c < H; c += 256) {
-        dst[c] = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]);
-        dst[H + c] = (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]);
+        dst[c] = wave_tree(red, 0, c);
+        dst[H + c] = wave_tree(red, 1, c);
     }
 }
 

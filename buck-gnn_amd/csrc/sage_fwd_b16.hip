@@ -13,7 +13,7 @@
 // epilogue. Slots: one per light-row block, then one per heavy row. A wave keeps its BatchNorm
 // sums in its own LDS rows between groups, added to once per group: carried in VGPRs across the
 // groups they took k_fwd_group<4, 8> from 100 to 116 registers and <8, 4> from 136 to 142
-// (DESIGN.md §3g); the block adds its four waves' rows in a fixed tree, as k_seg_sweep does.
+// (DESIGN.md §3g); the block adds its four waves' rows in a fixed tree, as spmm.hip's SageLds does.
 // No atomics; the summation order of every row and of every slot is fixed by the plan, so results
 // are deterministic run to run.
 #include "common.h"

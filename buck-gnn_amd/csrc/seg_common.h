@@ -1,8 +1,8 @@
 // Helpers shared by the CSR aggregation kernels (spmm.hip, and through b16_gather.h the bf16 ones:
 // sage_infer.hip, spmm_b16.hip, spmm_max_b16.hip), the tail (sage_tail.h) and the bf16 element-wise
-// kernels (elem.hip): the canonical SAGE row arithmetic,
-// the XCD sweep's row assignment, a lane's column positions, the MAX argmax state's layout and the
-// bf16 pack / unpack of one 16-byte vector.
+// kernels (elem.hip): the canonical SAGE row arithmetic, the XCD sweep's row assignment and grid, a
+// lane's column positions, the four-wave slot tree, the MAX argmax state's layout and the bf16
+// pack / unpack of one 16-byte vector.
 #pragma once
 
 #include "common.h"
@@ -13,8 +13,8 @@ namespace bgnn {
 __device__ __forceinline__ float inv_deg(int32_t d) { return __frcp_rn((float)(d > 0 ? d : 1)); }
 
 // Canonical SAGE row arithmetic, written with explicit roundings so that every kernel
-// (light, sweep, combine) produces bit-identical o / nrm regardless of how the
-// compiler would contract it: h = (a * sc + zr) + b, ss = fma(h, h, ss).
+// (blocked, sweep, combine: spmm.hip's sage_row) produces bit-identical o / nrm regardless of how
+// the compiler would contract it: h = (a * sc + zr) + b, ss = fma(h, h, ss).
 __device__ __forceinline__ float sage_h(float a, float sc, float zr, float b) {
     return __fadd_rn(__fadd_rn(__fmul_rn(a, sc), zr), b);
 }
@@ -48,6 +48,25 @@ __device__ __forceinline__ Sweep sweep_rows(int64_t n_rows, int wave) {
     s.first = lo + i * 4 + wave;
     s.T = s.first < hi ? (int)((hi - s.first + s.W - 1) / s.W) : 0;
     return s;
+}
+
+// The grid of a sweep kernel: at most one row / group per wave (4 per block), at most `cap` blocks,
+// a multiple of 8 (one share per XCD).
+inline int64_t grid8(int64_t waves_wanted, int64_t cap) {
+    int64_t blocks = (waves_wanted + 3) / 4;
+    if (blocks > cap) blocks = cap;
+    blocks = (blocks + 7) / 8 * 8;
+    return blocks < 8 ? 8 : blocks;
+}
+
+// The heavy rows' combine: the waves of its block (SUM / MEAN), each summing one contiguous run of
+// the row's chunks.
+constexpr int kCombineWaves = 16;
+
+// A block's slot from its four waves' LDS partials red[wave][q][c]: a fixed tree.
+template <int Q, int C>
+__device__ __forceinline__ float wave_tree(const float (&red)[4][Q][C], int q, int c) {
+    return (red[0][q][c] + red[1][q][c]) + (red[2][q][c] + red[3][q][c]);
 }
 
 // The MAX argmax state (bgnn_spmm_max_arg_bytes), written by bgnn_spmm_fwd(MAX) and

@@ -17,10 +17,17 @@
 // (super nodes, VirtualEdgeCreate.py:106-111) are skipped here and reduced by
 // `chunk`-edge pieces in k_seg_chunk, then combined in chunk order
 // (k_seg_combine) — deterministic, no atomics.
+//
+// Layout: one gather batch (gather_step) serves the blocked kernels (k_seg_light, k_seg_chunk,
+// through gather_range) and the sweep (k_seg_sweep); the row-group kernel (k_seg_group) has its own
+// batch over the plan's keys and shares the add (absorb_add). The plain epilogue is store_plain. The
+// SAGE epilogue is sage_row (the row arithmetic, all four callers, each with its own store) and, for
+// the light-row kernels, the block's SageLds (bias row, per-wave BatchNorm sums); k_seg_combine
+// writes its one row's sums itself. The host side (launch_all, light_kernel) picks the light-row
+// kernel: row groups, sweep or blocked. The knobs (SegTuning, common.h) are set through tuning.hip.
 #include <vector>
 
 #include "common.h"
-#include "gemm_common.h"
 #include "seg_common.h"
 
 namespace bgnn {
@@ -199,40 +206,50 @@ __device__ __forceinline__ void maxt_match(const SegArgs& A, int32_t i, int32_t 
     }
 }
 
-// Gather-accumulate the edges [e0, e1) of one row into acc. cols are shared by
-// the lanes of the row (wave-uniform when LPR == 64). `cpos[v]` = column offset
-// of this lane's v-th vector, `cok[v]` = whether it is inside H.
-template <int VEC, int NV, int OP, int U>
-__device__ __forceinline__ void gather_batch(const SegArgs& A, Acc<VEC, NV, OP>& acc, int32_t e,
-                                             int32_t nvalid, const int (&cpos)[NV],
-                                             const bool (&cok)[NV]) {
+// SUM / MEAN / MEANT: the accumulator after source element f of weight w (1 unless MEANT). A function
+// of values, so that k_seg_group's mask-bit branches stay scalar branches (b16_gather.h).
+__device__ __forceinline__ float absorb_add(float a, float f, float w, bool ok) {
+    return a + (ok ? __fmul_rn(f, w) : 0.f);
+}
+
+// One gather batch of a row: acc absorbs the edges at CSR positions e .. e + nvalid - 1, one per
+// slot; the slots from nvalid on re-read slot 0's row (L1 hit) and are masked out. Shared by the
+// blocked kernels (gather_range) and the sweep (k_seg_sweep), which differ in
+//   src(s)   the source row of slot s: col[e + s], or a readlane of the row's prefetched col vector
+//            (wave-uniform when LPR == 64);
+//   FILL     a vector outside H skips its load and is zero-filled (the blocked column tiles);
+//            otherwise it re-reads column 0, so the batch's loads carry no branch (the sweep).
+// `cpos[v]` = column offset of this lane's v-th vector, `cok[v]` = whether it is inside H.
+template <int VEC, int NV, int OP, int U, bool FILL, class Src>
+__device__ __forceinline__ void gather_step(const SegArgs& A, Acc<VEC, NV, OP>& acc, int32_t e, int32_t nvalid,
+                                            const int (&cpos)[NV], const bool (&cok)[NV], const Src& src) {
+    // keys: source row, MEANT weight, MAXT offset of the edge in its forward row
     int32_t j[U];
     float w[U];
-    int32_t off[(OP == OP_MAXT) ? U : 1];   // MAXT: the edge's offset in its forward row
+    int32_t off[(OP == OP_MAXT) ? U : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const int32_t eu = e + (u < nvalid ? u : 0);
-        j[u] = A.col[eu];
+        const int s = u < nvalid ? u : 0;
+        j[u] = src(s);
         w[u] = 1.f;
         if constexpr (OP == OP_MEANT) {
             const int32_t d = A.fwd_rowptr[j[u] + 1] - A.fwd_rowptr[j[u]];
             w[u] = inv_deg(d);
         }
-        if constexpr (OP == OP_MAXT) off[u] = A.perm_t[eu] - A.fwd_rowptr[j[u]];
+        if constexpr (OP == OP_MAXT) off[u] = A.perm_t[e + s] - A.fwd_rowptr[j[u]];
     }
+    // loads, all issued before the first use
     Vec<VEC> val[U][NV];
     uint32_t aw[(OP == OP_MAXT) ? U : 1][(OP == OP_MAXT) ? NV : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-            if (cok[v]) val[u][v] = ld<VEC>(A.x + (int64_t)j[u] * A.ldx + cpos[v]);
-            else {
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) val[u][v].f[k] = 0.f;
-            }
+            if (!FILL || cok[v]) val[u][v] = ld<VEC>(A.x + (int64_t)j[u] * A.ldx + (cok[v] ? cpos[v] : 0));
+            else val[u][v] = Vec<VEC>{};
             if constexpr (OP == OP_MAXT) aw[u][v] = maxt_bytes<VEC>(A, j[u], cok[v] ? cpos[v] : 0);
         }
+    // absorb
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const bool ok = u < nvalid;
@@ -252,21 +269,23 @@ __device__ __forceinline__ void gather_batch(const SegArgs& A, Acc<VEC, NV, OP>&
                 }
             } else {
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) acc.a[v][k] += ok ? __fmul_rn(val[u][v].f[k], w[u]) : 0.f;
+                for (int k = 0; k < VEC; ++k) acc.a[v][k] = absorb_add(acc.a[v][k], val[u][v].f[k], w[u], ok);
             }
         }
     }
 }
 
+// Gather-accumulate the edges [beg, end) of one row into acc, 8 per batch (a tail of at most 4: 4).
 template <int VEC, int NV, int OP>
 __device__ __forceinline__ void gather_range(const SegArgs& A, Acc<VEC, NV, OP>& acc, int32_t beg,
                                              int32_t end, const int (&cpos)[NV],
                                              const bool (&cok)[NV]) {
     int32_t e = beg;
-    for (; e + 8 <= end; e += 8) gather_batch<VEC, NV, OP, 8>(A, acc, e, 8, cpos, cok);
+    const auto src = [&](int s) { return A.col[e + s]; };
+    for (; e + 8 <= end; e += 8) gather_step<VEC, NV, OP, 8, true>(A, acc, e, 8, cpos, cok, src);
     const int32_t rem = end - e;
-    if (rem > 4) gather_batch<VEC, NV, OP, 8>(A, acc, e, rem, cpos, cok);
-    else if (rem > 0) gather_batch<VEC, NV, OP, 4>(A, acc, e, rem, cpos, cok);
+    if (rem > 4) gather_step<VEC, NV, OP, 8, true>(A, acc, e, rem, cpos, cok, src);
+    else if (rem > 0) gather_step<VEC, NV, OP, 4, true>(A, acc, e, rem, cpos, cok, src);
 }
 
 // Finish a plain reduction and store it (row r of out).
@@ -323,29 +342,26 @@ __device__ __forceinline__ void store_plain(const SegArgs& A, Acc<VEC, NV, OP>& 
     }
 }
 
-// Fused SAGE epilogue for one row held by a full wave (LPR == 64, VEC == 4):
-// h = acc*scale + z_r[r] + b; o = h / max(||h||, 1e-12); BN partial sums (the row arithmetic
-// is sage_h, seg_common.h).
-template <int NV, int OP>
-__device__ __forceinline__ void store_sage(const SegArgs& A, Acc<4, NV, OP>& acc, int64_t r,
-                                           int32_t deg, const int (&cpos)[NV], const bool (&cok)[NV],
-                                           float (&bs)[NV][4], float (&bq)[NV][4]) {
-    const float sc = (OP == OP_MEAN) ? inv_deg(deg) : 1.f;
+// Fused SAGE epilogue, the arithmetic of one row held by a full wave (LPR == 64, VEC == 4):
+// h = a*sc + z_r + b (sage_h, seg_common.h); o = h / max(||h||, 1e-12). Returns ||h||. bias: the bias
+// row, in LDS or global memory. put(v, o): what the caller does with the lane's v-th vector of o
+// (called for the vectors inside H only; a vector outside H takes part in the norm's wave sum with
+// zeros). The bias load is unconditional (a vector outside H re-reads column 0): under a per-lane
+// branch it cost k_seg_sweep<1, SUM, SAGE, 12> a wave per SIMD (93 -> 99 VGPRs), and a wrapper
+// around this function that took SegArgs by reference cost k_seg_group<2, *, SAGE, 4, 8> one
+// (125 -> 130); profiles/spmm_refactor_kres.txt.
+template <int NV, class Put>
+__device__ __forceinline__ float sage_row(const float (&a)[NV][4], float sc, const Vec<4> (&zr)[NV], const float* bias,
+                                          const int (&cpos)[NV], const bool (&cok)[NV], const Put& put) {
     float h[NV][4];
     float ss = 0.f;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-        if (cok[v]) {
-            const Vec<4> zr = ld<4>(A.zr + r * A.ldzr + cpos[v]);
-            const Vec<4> b = ld<4>(A.bias + cpos[v]);
+        const Vec<4> b = ld<4>(bias + (cok[v] ? cpos[v] : 0));
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                h[v][k] = sage_h(acc.a[v][k], sc, zr.f[k], b.f[k]);
-                ss = fmaf(h[v][k], h[v][k], ss);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) h[v][k] = 0.f;
+        for (int k = 0; k < 4; ++k) {
+            h[v][k] = cok[v] ? sage_h(a[v][k], sc, zr[v].f[k], b.f[k]) : 0.f;
+            ss = fmaf(h[v][k], h[v][k], ss);
         }
     }
     ss = group_sum(ss, kWave);
@@ -356,15 +372,53 @@ __device__ __forceinline__ void store_sage(const SegArgs& A, Acc<4, NV, OP>& acc
         if (!cok[v]) continue;
         Vec<4> o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            o.f[k] = h[v][k] / d;
-            bs[v][k] += o.f[k];
-            bq[v][k] += o.f[k] * o.f[k];
-        }
-        st<4>(A.out + r * A.ldo + cpos[v], o);
+        for (int k = 0; k < 4; ++k) o.f[k] = h[v][k] / d;
+        put(v, o);
     }
-    if ((threadIdx.x & 63) == 0) A.nrm[r] = n;
+    return n;
 }
+
+// SAGE epilogue state of a light-row block, in LDS: the bias row and each wave's BatchNorm partial
+// sums of o and o^2 (each lane owns its columns: no barriers between rows).
+struct SageLds {
+    float sum[4][2][512];
+    float bias[512];
+
+    // all threads of the block
+    template <int NV>
+    __device__ __forceinline__ void stage(const float* b, int H, int wave, const int (&cpos)[NV],
+                                          const bool (&cok)[NV]) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+            if (cok[v]) {
+                *reinterpret_cast<float4*>(&sum[wave][0][cpos[v]]) = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(&sum[wave][1][cpos[v]]) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        for (int c = threadIdx.x; c < H; c += 256) bias[c] = b[c];
+        __syncthreads();
+    }
+
+    // the wave's sums absorb the columns [c, c + 4) of one row
+    __device__ __forceinline__ void add(int wave, int c, const Vec<4>& o) {
+        float4* ps = reinterpret_cast<float4*>(&sum[wave][0][c]);
+        float4* pq = reinterpret_cast<float4*>(&sum[wave][1][c]);
+        float4 s = *ps, q = *pq;
+        s.x += o.f[0]; s.y += o.f[1]; s.z += o.f[2]; s.w += o.f[3];
+        q.x += o.f[0] * o.f[0]; q.y += o.f[1] * o.f[1]; q.z += o.f[2] * o.f[2]; q.w += o.f[3] * o.f[3];
+        *ps = s;
+        *pq = q;
+    }
+
+    // the block's slot: its four waves' sums, a fixed tree. All threads of the block.
+    __device__ __forceinline__ void store_slot(float* bn_partial, int H, int64_t slot) {
+        __syncthreads();
+        float* dst = bn_partial + slot * 2 * H;
+        for (int c = threadIdx.x; c < H; c += 256) {
+            dst[c] = wave_tree(sum, 0, c);
+            dst[H + c] = wave_tree(sum, 1, c);
+        }
+    }
+};
 
 // ---------------------------------------------------------------------------
 // Light rows: deg <= chunk. Grid: (blocks, column tiles). 256 threads.
@@ -382,13 +436,8 @@ __global__ __launch_bounds__(256) void k_seg_light(SegArgs A) {
     bool cok[NV];
     lane_cols<VEC, NV, LPR>(cb, lir, A.H, cpos, cok);
 
-    float bs[NV][4], bq[NV][4];
-    if constexpr (EPI == EPI_SAGE) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bs[v][k] = bq[v][k] = 0.f;
-    }
+    __shared__ __attribute__((aligned(16))) SageLds L;   // (SAGE only)
+    if constexpr (EPI == EPI_SAGE) L.stage<NV>(A.bias, A.H, wave, cpos, cok);
     uint32_t tmax = 0;
 
     for (int64_t rb = r_begin + (int64_t)wave * RPW; rb < r_end; rb += 4 * RPW) {
@@ -401,31 +450,21 @@ __global__ __launch_bounds__(256) void k_seg_light(SegArgs A) {
         acc.init();
         gather_range<VEC, NV, OP>(A, acc, beg, end, cpos, cok);
         if constexpr (EPI == EPI_SAGE) {
-            store_sage<NV, OP>(A, *reinterpret_cast<Acc<4, NV, OP>*>(&acc), r, deg, cpos, cok, bs, bq);
+            Vec<4> zr[NV];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) zr[v] = cok[v] ? ld<4>(A.zr + r * A.ldzr + cpos[v]) : Vec<4>{};
+            const float n = sage_row<NV>(acc.a, (OP == OP_MEAN) ? inv_deg(deg) : 1.f, zr, L.bias, cpos, cok,
+                                         [&](int v, const Vec<4>& o) {
+                                             st<4>(A.out + r * A.ldo + cpos[v], o);
+                                             L.add(wave, cpos[v], o);
+                                         });
+            if (lane == 0) A.nrm[r] = n;
         } else {
             store_plain<VEC, NV, OP>(A, acc, r, deg, cpos, cok, tmax);
         }
     }
     if constexpr (EPI == EPI_PLAIN) amax_flush_wave(A.amax, tmax);
-
-    if constexpr (EPI == EPI_SAGE) {
-        // block-reduce the BatchNorm partial sums over the 4 waves -> slot lb
-        __shared__ __attribute__((aligned(16))) float red[4][2][512];
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-            if (cok[v])
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    red[wave][0][cpos[v] + k] = bs[v][k];
-                    red[wave][1][cpos[v] + k] = bq[v][k];
-                }
-        __syncthreads();
-        float* dst = A.bn_partial + (int64_t)lb * 2 * A.H;
-        for (int c = threadIdx.x; c < A.H; c += 256) {
-            dst[c] = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]);
-            dst[A.H + c] = (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]);
-        }
-    }
+    if constexpr (EPI == EPI_SAGE) L.store_slot(A.bn_partial, A.H, lb);
 }
 
 // Heavy chunks: one wave per chunk -> partial[c, :]. 256 threads (4 chunks).
@@ -467,7 +506,7 @@ __global__ __launch_bounds__(256) void k_seg_chunk(SegArgs A) {
 // variant). A cfg3 super node has 79 chunks, so each wave loads 5 partial rows in one batch:
 // one memory round trip instead of three (4 waves: 17 us per launch; one wave: 44 us). MAX keeps
 // one wave walking the chunks in order (first-occurrence argmax), launched with 256 threads.
-constexpr int kCombineWaves = 16;
+// (kCombineWaves: seg_common.h)
 template <int VEC, int NV, int LPR, int OP, int EPI>
 __global__ __launch_bounds__(1024) void k_seg_combine(SegArgs A) {
     constexpr int W = (OP == OP_MAX) ? 1 : kCombineWaves;
@@ -550,22 +589,25 @@ __global__ __launch_bounds__(1024) void k_seg_combine(SegArgs A) {
     }
     if (wave != 0 || !act) return;
     if constexpr (EPI == EPI_SAGE) {
-        float bs[NV][4], bq[NV][4];
+        // the row's slot holds o and o^2 of this one row, as sums that started at +0 (a -0 in o
+        // is a +0 in the slot)
+        Vec<4> zr[NV];
 #pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bs[v][k] = bq[v][k] = 0.f;
-        store_sage<NV, OP>(A, *reinterpret_cast<Acc<4, NV, OP>*>(&acc), r, deg, cpos, cok, bs, bq);
+        for (int v = 0; v < NV; ++v) zr[v] = cok[v] ? ld<4>(A.zr + r * A.ldzr + cpos[v]) : Vec<4>{};
         float* dst = A.bn_partial + (int64_t)(A.light_slots + h) * 2 * A.H;
+        const float n = sage_row<NV>(acc.a, (OP == OP_MEAN) ? inv_deg(deg) : 1.f, zr, A.bias, cpos, cok,
+                                     [&](int v, const Vec<4>& o) {
+                                         Vec<4> s1, s2;
 #pragma unroll
-        for (int v = 0; v < NV; ++v)
-            if (cok[v]) {
-                Vec<4> s1, s2;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { s1.f[k] = bs[v][k]; s2.f[k] = bq[v][k]; }
-                st<4>(dst + cpos[v], s1);
-                st<4>(dst + A.H + cpos[v], s2);
-            }
+                                         for (int k = 0; k < 4; ++k) {
+                                             s1.f[k] = 0.f + o.f[k];
+                                             s2.f[k] = o.f[k] * o.f[k];
+                                         }
+                                         st<4>(A.out + r * A.ldo + cpos[v], o);
+                                         st<4>(dst + cpos[v], s1);
+                                         st<4>(dst + A.H + cpos[v], s2);
+                                     });
+        if (lane == 0) A.nrm[r] = n;
     } else {
         uint32_t tmax = 0;
         store_plain<VEC, NV, OP>(A, acc, r, deg, cpos, cok, tmax, OP == OP_MAX ? h : -1);
@@ -593,58 +635,6 @@ __global__ __launch_bounds__(1024) void k_seg_combine(SegArgs A) {
 // neighbour, deg <= chunk <= 64) issued one row ahead; up to U neighbours are
 // gathered in a single batch, so a light row costs about one memory round trip.
 // (Sweep / sweep_rows: seg_common.h)
-template <int NV, int OP, int U>
-__device__ __forceinline__ void sweep_gather(const SegArgs& A, Acc<4, NV, OP>& acc, int32_t cur, int32_t beg,
-                                             int32_t deg, int32_t e0, const int (&cpos)[NV], const bool (&cok)[NV]) {
-    const int nvalid = min(U, deg - e0);
-    int32_t j[U];
-    float w[U];
-    int32_t off[(OP == OP_MAXT) ? U : 1];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int slot = (u < nvalid) ? e0 + u : e0;   // masked slots re-read the first row (L1 hit)
-        j[u] = __builtin_amdgcn_readlane(cur, slot);
-        w[u] = 1.f;
-        if constexpr (OP == OP_MEANT) {
-            const int32_t d = A.fwd_rowptr[j[u] + 1] - A.fwd_rowptr[j[u]];
-            w[u] = inv_deg(d);
-        }
-        if constexpr (OP == OP_MAXT) off[u] = A.perm_t[beg + slot] - A.fwd_rowptr[j[u]];
-    }
-    Vec<4> val[U][NV];
-    uint32_t aw[(OP == OP_MAXT) ? U : 1][(OP == OP_MAXT) ? NV : 1];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            val[u][v] = ld<4>(A.x + (int64_t)j[u] * A.ldx + (cok[v] ? cpos[v] : 0));
-            if constexpr (OP == OP_MAXT) aw[u][v] = maxt_bytes<4>(A, j[u], cok[v] ? cpos[v] : 0);
-        }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const bool ok = u < nvalid;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            if constexpr (OP == OP_MAXT) {
-                bool m[4];
-                maxt_match<4>(A, j[u], off[u], cok[v] ? cpos[v] : 0, aw[u][v], ok && cok[v], m);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc.a[v][k] += m[k] ? val[u][v].f[k] : 0.f;
-            } else if constexpr (OP == OP_MAX) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const bool better = ok && (val[u][v].f[k] > acc.a[v][k]);
-                    acc.a[v][k] = better ? val[u][v].f[k] : acc.a[v][k];
-                    acc.g[v][k] = better ? (beg + e0 + u) : acc.g[v][k];
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc.a[v][k] += ok ? __fmul_rn(val[u][v].f[k], w[u]) : 0.f;
-            }
-        }
-    }
-}
-
 template <int NV, int OP, int EPI, int U>
 __global__ __launch_bounds__(256) void k_seg_sweep(SegArgs A) {
     const int lane = threadIdx.x & 63;
@@ -656,19 +646,9 @@ __global__ __launch_bounds__(256) void k_seg_sweep(SegArgs A) {
     lane_cols<4, NV, 64>(cb, lane, A.H, cpos, cok);
     // SAGE epilogue state lives in LDS, not VGPRs (it would cost 24 registers per lane and
     // the occupancy that a 12-neighbour gather batch needs): per-wave BatchNorm partial sums
-    // red[wave][0/1][col] (each lane owns its columns: no barriers) and the bias row.
-    __shared__ __attribute__((aligned(16))) float red[(EPI == EPI_SAGE) ? 4 : 1][2][(EPI == EPI_SAGE) ? 512 : 4];
-    __shared__ __attribute__((aligned(16))) float sbias[(EPI == EPI_SAGE) ? 512 : 4];
-    if constexpr (EPI == EPI_SAGE) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-            if (cok[v]) {
-                *reinterpret_cast<float4*>(&red[wave][0][cpos[v]]) = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4*>(&red[wave][1][cpos[v]]) = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        for (int c = threadIdx.x; c < A.H; c += 256) sbias[c] = A.bias[c];
-        __syncthreads();
-    }
+    // (each lane owns its columns: no barriers) and the bias row: SageLds.
+    __shared__ __attribute__((aligned(16))) SageLds L;   // (SAGE only)
+    if constexpr (EPI == EPI_SAGE) L.stage<NV>(A.bias, A.H, wave, cpos, cok);
     const int32_t chunk = A.chunk;
     uint32_t tmax = 0;
 
@@ -701,40 +681,15 @@ __global__ __launch_bounds__(256) void k_seg_sweep(SegArgs A) {
 #pragma unroll
                 for (int v = 0; v < NV; ++v) zr[v] = ld_nt(A.zr + r * A.ldzr + (cok[v] ? cpos[v] : 0));
             }
-            for (int e0 = 0; e0 < deg; e0 += U) sweep_gather<NV, OP, U>(A, acc, cur, beg, deg, e0, cpos, cok);
+            for (int e0 = 0; e0 < deg; e0 += U)
+                gather_step<4, NV, OP, U, false>(A, acc, beg + e0, min(U, deg - e0), cpos, cok,
+                                                 [&](int s) { return __builtin_amdgcn_readlane(cur, e0 + s); });
             if constexpr (EPI == EPI_SAGE) {
-                const float sc = (OP == OP_MEAN) ? inv_deg(deg) : 1.f;
-                float h[NV][4];
-                float ss = 0.f;
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    const float4 bv = cok[v] ? *reinterpret_cast<const float4*>(&sbias[cpos[v]])
-                                             : make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        h[v][q] = cok[v] ? sage_h(acc.a[v][q], sc, zr[v].f[q], bb[q]) : 0.f;
-                        ss = fmaf(h[v][q], h[v][q], ss);
-                    }
-                }
-                ss = group_sum(ss, kWave);
-                const float n = sqrtf(ss);
-                const float d = fmaxf(n, 1e-12f);
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    if (!cok[v]) continue;
-                    Vec<4> o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) o.f[q] = h[v][q] / d;
-                    st_nt(A.out + r * A.ldo + cpos[v], o);
-                    float4* ps = reinterpret_cast<float4*>(&red[wave][0][cpos[v]]);
-                    float4* pq = reinterpret_cast<float4*>(&red[wave][1][cpos[v]]);
-                    float4 a = *ps, b = *pq;
-                    a.x += o.f[0]; a.y += o.f[1]; a.z += o.f[2]; a.w += o.f[3];
-                    b.x += o.f[0] * o.f[0]; b.y += o.f[1] * o.f[1]; b.z += o.f[2] * o.f[2]; b.w += o.f[3] * o.f[3];
-                    *ps = a;
-                    *pq = b;
-                }
+                const float n = sage_row<NV>(acc.a, (OP == OP_MEAN) ? inv_deg(deg) : 1.f, zr, L.bias, cpos, cok,
+                                             [&](int v, const Vec<4>& o) {
+                                                 st_nt(A.out + r * A.ldo + cpos[v], o);
+                                                 L.add(wave, cpos[v], o);
+                                             });
                 if (lane == 0) A.nrm[r] = n;
             } else {
                 store_plain<4, NV, OP>(A, acc, r, deg, cpos, cok, tmax);
@@ -742,15 +697,7 @@ __global__ __launch_bounds__(256) void k_seg_sweep(SegArgs A) {
         }
     }
     if constexpr (EPI == EPI_PLAIN) amax_flush_wave(A.amax, tmax);
-
-    if constexpr (EPI == EPI_SAGE) {
-        __syncthreads();
-        float* dst = A.bn_partial + (int64_t)blockIdx.x * 2 * A.H;
-        for (int c = threadIdx.x; c < A.H; c += 256) {
-            dst[c] = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]);
-            dst[A.H + c] = (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]);
-        }
-    }
+    if constexpr (EPI == EPI_SAGE) L.store_slot(A.bn_partial, A.H, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -774,18 +721,8 @@ __global__ __launch_bounds__(256) void k_seg_group(SegArgs A) {
     int cpos[NV];
     bool cok[NV];
     lane_cols<4, NV, 64>(0, lane, A.H, cpos, cok);
-    __shared__ __attribute__((aligned(16))) float red[(EPI == EPI_SAGE) ? 4 : 1][2][(EPI == EPI_SAGE) ? 512 : 4];
-    __shared__ __attribute__((aligned(16))) float sbias[(EPI == EPI_SAGE) ? 512 : 4];
-    if constexpr (EPI == EPI_SAGE) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-            if (cok[v]) {
-                *reinterpret_cast<float4*>(&red[wave][0][cpos[v]]) = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4*>(&red[wave][1][cpos[v]]) = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        for (int c = threadIdx.x; c < A.H; c += 256) sbias[c] = A.bias[c];
-        __syncthreads();
-    }
+    __shared__ __attribute__((aligned(16))) SageLds L;   // (SAGE only)
+    if constexpr (EPI == EPI_SAGE) L.stage<NV>(A.bias, A.H, wave, cpos, cok);
     const int32_t chunk = A.chunk;
     uint32_t tmax = 0;
 
@@ -830,13 +767,9 @@ __global__ __launch_bounds__(256) void k_seg_group(SegArgs A) {
                 sl_n = lane < c ? A.gsrc[b + lane] : 0;
                 ml_n = lane < c ? (uint32_t)A.gmask[b + lane] : 0u;
             }
-            float a[R][NV][4];
+            Acc<4, NV, OP> a[R];
 #pragma unroll
-            for (int t = 0; t < R; ++t)
-#pragma unroll
-                for (int v = 0; v < NV; ++v)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) a[t][v][q] = 0.f;
+            for (int t = 0; t < R; ++t) a[t].init();
             for (int32_t eb = 0; eb < cnt; eb += 64) {
                 const int n = min(64, cnt - eb);
                 int32_t sl = sl0;
@@ -879,88 +812,41 @@ __global__ __launch_bounds__(256) void k_seg_group(SegArgs A) {
                                 for (int v = 0; v < NV; ++v)
 #pragma unroll
                                     for (int q = 0; q < 4; ++q)
-                                        a[t][v][q] += (OP == OP_MEANT) ? __fmul_rn(val[u][v].f[q], w[u])
-                                                                       : val[u][v].f[q];
+                                        a[t].a[v][q] = absorb_add(a[t].a[v][q], val[u][v].f[q], w[u], true);
                             }
                         }
                 }
             }
+            Vec<4> zr[R][NV];
             if constexpr (EPI == EPI_SAGE) {
-                Vec<4> zr[R][NV];
 #pragma unroll
                 for (int t = 0; t < R; ++t) {
                     const int64_t r = r0 + (t < rows ? t : 0);
 #pragma unroll
                     for (int v = 0; v < NV; ++v) zr[t][v] = ld_nt(A.zr + r * A.ldzr + (cok[v] ? cpos[v] : 0));
                 }
+            }
 #pragma unroll
-                for (int t = 0; t < R; ++t) {
-                    const int64_t r = r0 + t;
-                    const int32_t rb = __builtin_amdgcn_readlane(rp, t);
-                    const int32_t deg = __builtin_amdgcn_readlane(rp, t + 1) - rb;
-                    if (t >= rows || deg > chunk) continue;   // heavy row: chunk + combine
-                    const float sc = (OP == OP_MEAN) ? inv_deg(deg) : 1.f;
-                    float h[NV][4];
-                    float ss = 0.f;
-#pragma unroll
-                    for (int v = 0; v < NV; ++v) {
-                        const float4 bv = cok[v] ? *reinterpret_cast<const float4*>(&sbias[cpos[v]])
-                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
-                        const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            h[v][q] = cok[v] ? sage_h(a[t][v][q], sc, zr[t][v].f[q], bb[q]) : 0.f;
-                            ss = fmaf(h[v][q], h[v][q], ss);
-                        }
-                    }
-                    ss = group_sum(ss, kWave);
-                    const float nr = sqrtf(ss);
-                    const float d = fmaxf(nr, 1e-12f);
-#pragma unroll
-                    for (int v = 0; v < NV; ++v) {
-                        if (!cok[v]) continue;
-                        Vec<4> o;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) o.f[q] = h[v][q] / d;
-                        st_nt(A.out + r * A.ldo + cpos[v], o);
-                        float4* ps = reinterpret_cast<float4*>(&red[wave][0][cpos[v]]);
-                        float4* pq = reinterpret_cast<float4*>(&red[wave][1][cpos[v]]);
-                        float4 s1 = *ps, s2 = *pq;
-                        s1.x += o.f[0]; s1.y += o.f[1]; s1.z += o.f[2]; s1.w += o.f[3];
-                        s2.x += o.f[0] * o.f[0]; s2.y += o.f[1] * o.f[1];
-                        s2.z += o.f[2] * o.f[2]; s2.w += o.f[3] * o.f[3];
-                        *ps = s1;
-                        *pq = s2;
-                    }
-                    if (lane == 0) A.nrm[r] = nr;
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < R; ++t) {
-                    const int64_t r = r0 + t;
-                    const int32_t rb = __builtin_amdgcn_readlane(rp, t);
-                    const int32_t deg = __builtin_amdgcn_readlane(rp, t + 1) - rb;
-                    if (t >= rows || deg > chunk) continue;
-                    Acc<4, NV, OP> acc;
-#pragma unroll
-                    for (int v = 0; v < NV; ++v)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) acc.a[v][q] = a[t][v][q];
-                    store_plain<4, NV, OP>(A, acc, r, deg, cpos, cok, tmax);
+            for (int t = 0; t < R; ++t) {
+                const int64_t r = r0 + t;
+                const int32_t rb = __builtin_amdgcn_readlane(rp, t);
+                const int32_t deg = __builtin_amdgcn_readlane(rp, t + 1) - rb;
+                if (t >= rows || deg > chunk) continue;   // heavy row: chunk + combine
+                if constexpr (EPI == EPI_SAGE) {
+                    const float n = sage_row<NV>(a[t].a, (OP == OP_MEAN) ? inv_deg(deg) : 1.f, zr[t], L.bias, cpos, cok,
+                                                 [&](int v, const Vec<4>& o) {
+                                                     st_nt(A.out + r * A.ldo + cpos[v], o);
+                                                     L.add(wave, cpos[v], o);
+                                                 });
+                    if (lane == 0) A.nrm[r] = n;
+                } else {
+                    store_plain<4, NV, OP>(A, a[t], r, deg, cpos, cok, tmax);
                 }
             }
         }
     }
     if constexpr (EPI == EPI_PLAIN) amax_flush_wave(A.amax, tmax);
-
-    if constexpr (EPI == EPI_SAGE) {
-        __syncthreads();
-        float* dst = A.bn_partial + (int64_t)blockIdx.x * 2 * A.H;
-        for (int c = threadIdx.x; c < A.H; c += 256) {
-            dst[c] = (red[0][0][c] + red[1][0][c]) + (red[2][0][c] + red[3][0][c]);
-            dst[A.H + c] = (red[0][1][c] + red[1][1][c]) + (red[2][1][c] + red[3][1][c]);
-        }
-    }
+    if constexpr (EPI == EPI_SAGE) L.store_slot(A.bn_partial, A.H, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -970,13 +856,14 @@ constexpr int kMaxLightBlocks = 1024;
 // (ABI 12 removed BGNN_TUNE_MAX_GROUP, the max forward on the row-group kernel: bit-identical, but
 // cfg2 156 -> 168 us, the per-(key, row) argmax resolution and tie test outweighing the
 // deduplicated loads; round 5, profiles/r05_bench_max_group_j.json)
-static int g_seg_kernel = 0;     // 0 = auto (row-group kernel where planned, else sweep), 1 = blocked,
-                                 // 2 = sweep
-static int g_grp_blocks = 1024;  // row-group kernel grid (4 blocks of 4 waves per CU)
-static int g_seg_blocks = 1024;  // sweep grid (rounded to a multiple of 8)
-static int g_seg_nt = 1;         // non-temporal hints on stream-once data (default on: +8 % fwd)
-static int g_seg_u = 0;          // neighbours per gather batch in the sweep kernel (0 = auto = 12:
-                                 // mesh rows have 8 neighbours + ~1 virtual edge, one batch)
+SegTuning g_seg = {
+    0,      // kernel: 0 = auto (row-group kernel where planned, else sweep), 1 = blocked, 2 = sweep
+    1024,   // grp_blocks: row-group kernel grid (4 blocks of 4 waves per CU)
+    1024,   // blocks: sweep grid (rounded to a multiple of 8)
+    1,      // nt: non-temporal hints on stream-once data (default on: +8 % fwd)
+    0,      // u: neighbours per gather batch in the sweep kernel (0 = auto = 12: mesh rows have 8
+            // neighbours + ~1 virtual edge, one batch)
+};
 
 struct Geometry {
     int vec, nv, lpr, ctiles;
@@ -1015,22 +902,6 @@ inline int64_t light_grid(int64_t n_rows, int rows_per_wave, int max_blocks, int
     return blocks;
 }
 
-inline int64_t sweep_grid(int64_t n_rows) {
-    int64_t want = (n_rows + 3) / 4;                 // at most one row per wave
-    int64_t blocks = g_seg_blocks;
-    if (want < blocks) blocks = want;
-    blocks = (blocks + 7) / 8 * 8;
-    return blocks < 8 ? 8 : blocks;
-}
-
-inline int64_t group_grid(int64_t G) {
-    int64_t want = (G + 3) / 4;                      // at most one group per wave
-    int64_t blocks = g_grp_blocks;
-    if (want < blocks) blocks = want;
-    blocks = (blocks + 7) / 8 * 8;
-    return blocks < 8 ? 8 : blocks;
-}
-
 // Optional timing of the heavy-row (super node) launches: while enabled, every launch_all with
 // chunks records a HIP event pair around its k_seg_chunk + k_seg_combine launches (bench.py's
 // cfg3 block reports the super rows' share of the aggregation; bgnn_heavy_timing).
@@ -1057,12 +928,29 @@ inline HeavyEv* heavy_ev_next(int fwd) {
 
 // Whether launch_all runs the row-group kernel for this CSR / reduce.
 inline bool use_group(const SegArgs& A, int op, int vec, int lpr) {
-    return g_seg_kernel == 0 && A.gcnt != nullptr && vec == 4 && lpr == 64 && A.chunk <= 64 &&
+    return g_seg.kernel == 0 && A.gcnt != nullptr && vec == 4 && lpr == 64 && A.chunk <= 64 &&
            (op == OP_SUM || op == OP_MEAN || op == OP_MEANT);
 }
 
 inline int64_t light_blocks_sage(const SegArgs& A) {
-    return use_group(A, OP_SUM, 4, 64) ? group_grid(A.n_groups) : sweep_grid(A.n_rows);
+    return use_group(A, OP_SUM, 4, 64) ? grid8(A.n_groups, g_seg.grp_blocks) : grid8(A.n_rows, g_seg.blocks);
+}
+
+// The light-row kernel of a launch: the row-group kernel, else the sweep at the knob's U, else the
+// blocked kernel.
+template <int VEC, int NV, int LPR, int OP, int EPI>
+auto light_kernel(const SegArgs& A, bool group, bool sweep) -> void (*)(SegArgs) {
+    if constexpr (VEC == 4 && LPR == 64) {
+        if constexpr (OP == OP_SUM || OP == OP_MEAN || OP == OP_MEANT) {
+            if (group) return A.group_rows == 8 ? k_seg_group<NV, OP, EPI, 8, 4> : k_seg_group<NV, OP, EPI, 4, 8>;
+        }
+        if (sweep) {
+            const int u = g_seg.u ? g_seg.u : 12;
+            return u == 8 ? k_seg_sweep<NV, OP, EPI, 8> : u == 16 ? k_seg_sweep<NV, OP, EPI, 16>
+                                                                  : k_seg_sweep<NV, OP, EPI, 12>;
+        }
+    }
+    return k_seg_light<VEC, NV, LPR, OP, EPI>;
 }
 
 template <int VEC, int NV, int LPR, int OP, int EPI>
@@ -1070,18 +958,18 @@ int launch_all(SegArgs A, int ctiles, int max_blocks, hipStream_t s, int64_t* bl
     int64_t rpb = 0;
     const bool group = use_group(A, OP, VEC, LPR) && ctiles == 1;   // one wave holds a whole row
     // the sweep kernel needs one row per wave and every light row's list in one vector load
-    const bool sweep = (VEC == 4 && LPR == 64 && g_seg_kernel != 1 && A.chunk <= 64);
+    const bool sweep = (VEC == 4 && LPR == 64 && g_seg.kernel != 1 && A.chunk <= 64);
     int64_t blocks;
     if (group) {
-        blocks = group_grid(A.n_groups);
+        blocks = grid8(A.n_groups, g_seg.grp_blocks);
     } else if (sweep || EPI == EPI_SAGE) {   // SAGE: slot count = bgnn_sage_fwd_slots() for either kernel
-        blocks = sweep_grid(A.n_rows);
+        blocks = grid8(A.n_rows, g_seg.blocks);
         rpb = (A.n_rows + blocks - 1) / blocks;
     } else {
         blocks = light_grid(A.n_rows, kWave / LPR, max_blocks, &rpb);
     }
     A.rows_per_block = rpb;
-    A.nt = g_seg_nt;
+    A.nt = g_seg.nt;
     // BGNN_TUNE_ROWS_REV bit 2 (SAGE epilogue) / bit 3 (plain): sweep each eighth downward, so it
     // starts on the rows the producing GEMM (which walks its tiles upward, one eighth per XCD)
     // wrote last
@@ -1089,37 +977,8 @@ int launch_all(SegArgs A, int ctiles, int max_blocks, hipStream_t s, int64_t* bl
     if (blocks_out) *blocks_out = blocks;
     A.light_slots = (int32_t)blocks;
     if (A.n_rows > 0) {
-        if constexpr (VEC == 4 && LPR == 64 && (OP == OP_SUM || OP == OP_MEAN || OP == OP_MEANT)) {
-            if (group) {
-                const dim3 gr((unsigned)blocks);
-                if (A.group_rows == 8)
-                    hipLaunchKernelGGL((k_seg_group<NV, OP, EPI, 8, 4>), gr, dim3(256), 0, s, A);
-                else
-                    hipLaunchKernelGGL((k_seg_group<NV, OP, EPI, 4, 8>), gr, dim3(256), 0, s, A);
-                BGNN_CHECK_LAUNCH();
-            }
-        }
-        if (group) {
-        } else if constexpr (VEC == 4 && LPR == 64) {
-            if (sweep) {
-                const int u = g_seg_u ? g_seg_u : 12;
-                if (u == 8)
-                    hipLaunchKernelGGL((k_seg_sweep<NV, OP, EPI, 8>), dim3((unsigned)blocks, ctiles), dim3(256), 0,
-                                       s, A);
-                else if (u == 16)
-                    hipLaunchKernelGGL((k_seg_sweep<NV, OP, EPI, 16>), dim3((unsigned)blocks, ctiles), dim3(256), 0,
-                                       s, A);
-                else
-                    hipLaunchKernelGGL((k_seg_sweep<NV, OP, EPI, 12>), dim3((unsigned)blocks, ctiles), dim3(256), 0,
-                                       s, A);
-            } else {
-                hipLaunchKernelGGL((k_seg_light<VEC, NV, LPR, OP, EPI>), dim3((unsigned)blocks, ctiles), dim3(256),
-                                   0, s, A);
-            }
-        } else {
-            hipLaunchKernelGGL((k_seg_light<VEC, NV, LPR, OP, EPI>), dim3((unsigned)blocks, ctiles), dim3(256), 0,
-                               s, A);
-        }
+        hipLaunchKernelGGL((light_kernel<VEC, NV, LPR, OP, EPI>(A, group, sweep)), dim3((unsigned)blocks, ctiles),
+                           dim3(256), 0, s, A);
         BGNN_CHECK_LAUNCH();
     }
     if (A.n_chunks > 0) {
@@ -1208,7 +1067,7 @@ int seg_combine_plain(const bgnn_csr_t* csr, int32_t H, int32_t reduce, float* p
     A.H = H;
     A.out = out; A.ldo = H;
     A.partial = partial;
-    A.nt = g_seg_nt;
+    A.nt = g_seg.nt;
     const dim3 grid(A.n_heavy, (H + 511) / 512);
     if (reduce == BGNN_REDUCE_MEAN)
         hipLaunchKernelGGL((k_seg_combine<4, 2, 64, OP_MEAN, EPI_PLAIN>), grid, dim3(64 * kCombineWaves), 0, s, A);
@@ -1217,12 +1076,6 @@ int seg_combine_plain(const bgnn_csr_t* csr, int32_t H, int32_t reduce, float* p
     BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }
-
-extern int g_x6_bdma;   // gemm_x6.hip
-extern int g_h3p_nsb;   // gemm_h3p.hip
-#ifdef BGNN_H3P_ABLATION
-extern int g_h3p_abl;
-#endif
 
 }  // namespace bgnn
 
@@ -1346,71 +1199,6 @@ extern "C" int32_t bgnn_sage_fwd_slots(const bgnn_csr_t* csr) {
     if (!csr) return -1;
     const SegArgs A = args_from_csr(csr);
     return (int32_t)(light_blocks_sage(A) + (csr->n_chunks > 0 ? csr->n_heavy : 0));
-}
-
-extern "C" int32_t bgnn_get_tuning(int32_t knob) {
-    switch (knob) {
-        case BGNN_TUNE_SEG_KERNEL: return g_seg_kernel;
-        case BGNN_TUNE_SEG_BLOCKS: return g_seg_blocks;
-        case BGNN_TUNE_SEG_U: return g_seg_u;
-        case BGNN_TUNE_SEG_NT: return g_seg_nt;
-        case BGNN_TUNE_GEMM_MODE: return gemm_mode();
-        case BGNN_TUNE_ROWS_NT: return rows_nt();
-        case BGNN_TUNE_GROUP_BLOCKS: return g_grp_blocks;
-        case BGNN_TUNE_ROWS_REV: return rows_rev();
-        case BGNN_TUNE_GEMM_BDMA: return g_x6_bdma == 2 && g_h3p_nsb == 4 ? 3 : g_x6_bdma;
-        default: return -1;
-    }
-}
-
-extern "C" int bgnn_set_tuning(int32_t knob, int32_t value) {
-    switch (knob) {
-        case BGNN_TUNE_SEG_KERNEL:
-            BGNN_REQUIRE(value >= 0 && value <= 2, "set_tuning: kernel must be 0 (auto), 1 (blocked) or 2 (sweep)");
-            g_seg_kernel = value;
-            return BGNN_OK;
-        case BGNN_TUNE_SEG_BLOCKS:
-            BGNN_REQUIRE(value >= 8 && value <= 65536, "set_tuning: blocks out of range");
-            g_seg_blocks = value;
-            return BGNN_OK;
-        case BGNN_TUNE_SEG_U:
-            BGNN_REQUIRE(value == 0 || value == 8 || value == 12 || value == 16,
-                         "set_tuning: U must be 0 (auto), 8, 12 or 16");
-            g_seg_u = value;
-            return BGNN_OK;
-        case BGNN_TUNE_SEG_NT: g_seg_nt = value ? 1 : 0; return BGNN_OK;
-        case BGNN_TUNE_GROUP_BLOCKS:
-            BGNN_REQUIRE(value >= 8 && value <= 65536, "set_tuning: group blocks out of range");
-            g_grp_blocks = value;
-            return BGNN_OK;
-        case BGNN_TUNE_ROWS_NT: set_rows_nt(value); return BGNN_OK;
-        case BGNN_TUNE_ROWS_REV: set_rows_rev(value); return BGNN_OK;
-        case BGNN_TUNE_GEMM_BDMA:
-#ifdef BGNN_H3P_ABLATION
-            if (value >= 16) {   // measurement build: the pipelined kernel (4 slots) with ablation value / 16
-                g_x6_bdma = 2;
-                g_h3p_nsb = 4;
-                g_h3p_abl = value / 16;
-                return BGNN_OK;
-            }
-            g_h3p_abl = 0;
-#endif
-#ifdef BGNN_H3P_ABLATION
-            BGNN_REQUIRE(value >= 0 && value <= 4, "set_tuning: gemm B staging must be 0 .. 4");
-#else
-            BGNN_REQUIRE(value == 0 || value == 2 || value == 3,
-                         "set_tuning: gemm B staging must be 0 (k_gemm_x6, register copy) or 2 / 3 (the pipelined "
-                         "kernel, 3 / 4 slots); 1 and 4 are measurement-build forms (make abl)");
-#endif
-            g_x6_bdma = value == 3 ? 2 : value;
-            g_h3p_nsb = value == 3 ? 4 : 3;
-            return BGNN_OK;
-        case BGNN_TUNE_GEMM_MODE:
-            BGNN_REQUIRE(value == 0 || value == 2, "set_tuning: gemm mode must be 0 (f32 MFMA) or 2 (f16x3)");
-            set_gemm_mode(value);
-            return BGNN_OK;
-        default: return fail(BGNN_E_ARG, "set_tuning: unknown knob %d", knob);
-    }
 }
 
 extern "C" int bgnn_sage_fwd(const bgnn_csr_t* csr, const float* zl, int64_t ldzl, const float* zr, int64_t ldzr,

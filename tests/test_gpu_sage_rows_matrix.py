@@ -137,8 +137,8 @@ def test_a_sage_fwd(dev, case):
     slots = _lib.query("bgnn_sage_fwd_slots", csr.ref())
     assert slots == R.fwd_slots(n, nh if nck else 0, groups), f"{label}: {slots} slots"
     assert slots > (nh if nck else 0) and (slots - (nh if nck else 0)) % 8 == 0
-    runs = []
-    for _ in range(2):
+
+    def run():
         o, nrm, part = Out(dev, n, H, ld=H), Out(dev, 1, n), Out(dev, slots, 2 * H, ld=2 * H)
         scratch = Out(dev, 1, max(nck, 1) * H)
         _lib.call("bgnn_sage_fwd", csr.ref(), pzl, ldz, pzr, ldz, ptr(bbuf), H, mean, ptr(o), ptr(nrm), ptr(part),
@@ -146,7 +146,9 @@ def test_a_sage_fwd(dev, case):
         torch.cuda.synchronize()
         for w, nm in ((o, "o"), (nrm, "nrm"), (part, "bn_partial"), (scratch, "chunk scratch")):
             w.guard(f"{label} {nm}")
-        runs.append((o.read(), nrm.read().view(n), part.read().view(slots, 2, H)))
+        return o.read(), nrm.read().view(n), part.read().view(slots, 2, H)
+
+    runs = [run(), run()]
     ko, kn, P = runs[0]
     check("A sage_fwd o", ko, ref["o"], ref["o_bound"], label + " o")
     check("A sage_fwd nrm", kn, ref["nrm"], ref["nrm_bound"], label + " nrm")
@@ -159,6 +161,14 @@ def test_a_sage_fwd(dev, case):
     check("A sage_fwd sum o^2", P[:, 1].to(D).sum(0), s, bound, f"{label} column sums of o^2 (R = {Rr})")
     for a, b2, nm in zip(runs[0], runs[1], ("o", "nrm", "bn_partial")):
         assert torch.equal(a, b2), f"{label}: {nm} differs between two runs"
+    if kind == "blocked":
+        # every kernel runs one row arithmetic (seg_common.h): the one-row-per-wave kernel's o and nrm are the
+        # blocked kernel's bit for bit (bn_partial is not compared: the slots partition the rows differently)
+        _lib.call("bgnn_set_tuning", 1, 2)
+        assert _lib.query("bgnn_sage_fwd_slots", csr.ref()) == slots
+        so, sn, _ = run()
+        assert torch.equal(so, ko), f"{label}: o differs from the one-row-per-wave kernel's"
+        assert torch.equal(sn, kn), f"{label}: nrm differs from the one-row-per-wave kernel's"
 
 
 # ============================================================================ B. bgnn_sage_apply

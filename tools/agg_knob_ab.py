@@ -3,7 +3,7 @@
 training step runs them: the fused SAGE forward (bgnn_sage_fwd, z interleaved [N, 2H]) and the
 transpose aggregation (bgnn_spmm_bwd, dh = dz[:, H:] -> dz[:, :H]); 1 GiB cache flush between
 launches, median HIP-event times, bit-identity against the first setting.
-    python tools/agg_knob_ab.py [--config cfg2] [--rounds 15] "" "7=2048" ..."""
+    python tools/agg_knob_ab.py [--config cfg2] [--rounds 15] [--hidden 512] "" "7=2048" ..."""
 import argparse
 import os
 import sys
@@ -72,6 +72,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--group-rows", type=int, default=4)
+    ap.add_argument("--hidden", type=int, default=512, help="H (a multiple of 4, at most 512)")
     ap.add_argument("--reorder", action="store_true", help="strip-pair node order (bgnn.store.cluster_order)")
     ap.add_argument("settings", nargs="*", default=[""])
     args = ap.parse_args()
@@ -92,7 +93,7 @@ def main():
             inv[lo + perm] = lo + np.arange(hi - lo)
         ei = torch.from_numpy(np.stack([inv[src], inv[dst]]))
     g = Graph.build(ei.to(dev), b.num_nodes)
-    N, E, H = b.num_nodes, b.num_edges, 512
+    N, E, H = b.num_nodes, b.num_edges, args.hidden
     torch.manual_seed(0)
     z = torch.randn(N, 2 * H, device=dev)
     dz = torch.randn(N, 2 * H, device=dev)
