@@ -39,7 +39,6 @@ __global__ __launch_bounds__(256) void k_bn_colsums(const float* __restrict__ a,
                                                     const float* __restrict__ mean, const float* __restrict__ invstd,
                                                     int64_t n_rows, int C, int64_t rows_per_block,
                                                     float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float red[256][8];
     const int C4 = C / 4, rpi = 256 / C4;
     const int t = threadIdx.x, c4 = t % C4, ph = t / C4, c = c4 * 4;
     const int lb = xcd_remap(blockIdx.x, gridDim.x);
@@ -69,18 +68,7 @@ __global__ __launch_bounds__(256) void k_bn_colsums(const float* __restrict__ a,
             for (int k = 0; k < 4; ++k) { s0[k] += aa[k]; s1[k] += aa[k] * ((xx[k] - mu[k]) * is[k]); }
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { red[t][k] = s0[k]; red[t][4 + k] = s1[k]; }
-    __syncthreads();
-    if (t < C4) {
-        float a0[4] = {0.f, 0.f, 0.f, 0.f}, a1[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int q = 0; q < rpi; ++q)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { a0[k] += red[q * C4 + t][k]; a1[k] += red[q * C4 + t][4 + k]; }
-        float* dst = part + (int64_t)lb * 2 * C;
-        *reinterpret_cast<float4*>(dst + c) = make_float4(a0[0], a0[1], a0[2], a0[3]);
-        *reinterpret_cast<float4*>(dst + C + c) = make_float4(a1[0], a1[1], a1[2], a1[3]);
-    }
+    block_col_partials(s0, s1, C, part + (int64_t)lb * 2 * C);
 }
 
 // y = x * scale + shift (forward), or the train-mode input gradient

@@ -62,6 +62,40 @@ __device__ __forceinline__ float group_sum(float v, int width) {
     return v;
 }
 
+// Fold a thread's running max |value| (f32 bits) into *amax: block max over 256 threads,
+// then one atomic per block (same-address atomics serialise in L2). Must be reached by every
+// thread of the block.
+__device__ __forceinline__ void block_amax(uint32_t* amax, uint32_t m) {
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, kWave));
+    __shared__ uint32_t red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = max(max(red[0], red[1]), max(red[2], red[3]));
+        if (m) atomicMax(amax, m);
+    }
+}
+
+// Store tail of a column-sum pass over [rows, C] with C4 = C / 4 threads per row and 256 / C4 row
+// phases per block: thread t = ph * C4 + c4 brings the two sums s0 / s1 of its float4 column over
+// its phase's rows; they are added over the phases in phase order and stored as the two halves of
+// the block's partial slot dst[2][C]. Must be reached by every thread of the block.
+__device__ __forceinline__ void block_col_partials(const float (&s0)[4], const float (&s1)[4], int C, float* dst) {
+    __shared__ __attribute__((aligned(16))) float red[256][8];
+    const int C4 = C / 4, rpi = 256 / C4, t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { red[t][k] = s0[k]; red[t][4 + k] = s1[k]; }
+    __syncthreads();
+    if (t < C4) {
+        float a0[4] = {0.f, 0.f, 0.f, 0.f}, a1[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < rpi; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { a0[k] += red[q * C4 + t][k]; a1[k] += red[q * C4 + t][4 + k]; }
+        *reinterpret_cast<float4*>(dst + 4 * t) = make_float4(a0[0], a0[1], a0[2], a0[3]);
+        *reinterpret_cast<float4*>(dst + C + 4 * t) = make_float4(a1[0], a1[1], a1[2], a1[3]);
+    }
+}
+
 // Counter-based dropout hash: 64 random bits for (seed, 4-element group index).
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
@@ -85,6 +119,16 @@ static inline uint32_t dropout_threshold(float p) {
     double t = (double)p * 65536.0 + 0.5;
     if (t > 65536.0) t = 65536.0;
     return (uint32_t)t;
+}
+
+// Dropout(p) as the row kernels take it: the keep threshold and the kept elements' scale
+struct Dropout {
+    uint32_t thr;
+    float inv_keep;
+};
+static inline Dropout dropout_of(float p) {
+    const uint32_t thr = dropout_threshold(p);
+    return {thr, thr ? 1.f / (1.f - p) : 1.f};
 }
 
 // GEMM kernel family (gemm.hip): 0 = f32 MFMA, 1 = bf16x6, 2 = f16x3 (f32-accurate split products)

@@ -288,14 +288,7 @@ __global__ __launch_bounds__(256) void k_fold_maxima(FoldMaxArgs a) {
         for (int64_t i = b * 256 + threadIdx.x; i < n; i += nb * 256)
             m = max(m, __float_as_uint(P[(i / cols) * ld + i % cols]) & 0x7fffffffu);
     }
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, kWave));
-    __shared__ uint32_t red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (m) atomicMax(a.out + pi, m);
-    }
+    block_amax(a.out + pi, m);
 }
 
 // one product of the chain as the GEMM planner plans it, on bm x bn workgroup tiles; false: not the

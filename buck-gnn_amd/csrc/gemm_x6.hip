@@ -82,14 +82,7 @@ __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ P, int
             }
         }
     }
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, kWave));
-    __shared__ uint32_t red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (m) atomicMax(out, m);
-    }
+    block_amax(out, m);
 }
 
 // max |W_i| of n items of equal shape (rows x cols, ld; item i at P + i * item_stride) in one
@@ -110,14 +103,7 @@ __global__ __launch_bounds__(256) void k_absmax_items(const float* __restrict__ 
                            max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu)));
         }
     }
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, kWave));
-    __shared__ uint32_t red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (m) atomicMax(out + (int64_t)blockIdx.y * out_stride, m);
-    }
+    block_amax(out + (int64_t)blockIdx.y * out_stride, m);
 }
 
 void launch_absmax(const float* P, int64_t rows, int64_t cols, int64_t ld, int64_t blk, int64_t pstride,

@@ -9,6 +9,9 @@
 // The backward recomputes the hidden layer from x (cheaper than storing [N, 64]) and
 // accumulates the weight and bias gradients of both layers per workgroup; a second kernel sums
 // the per-workgroup partials in a fixed order (deterministic, no atomics).
+//
+// Below them: the decoder's small-batch Linears (k_small_linear_*) and the output-gradient prep of
+// a dense Linear's backward (k_linear_bwd_prep, f32 and bf16: mask, bias partials, max|g|).
 #include "common.h"
 
 namespace bgnn {
@@ -401,6 +404,135 @@ __global__ __launch_bounds__(256) void k_small_linear_bwd_x(const float* __restr
 
 }  // namespace
 
+// ---------------------------------------------------------------------------
+// Output-gradient prep of a dense Linear (the encoder MLP's LinearFn.backward,
+// Models/BuckGNN.py:67-74) in one pass over g [N, C]: the fused ReLU's mask
+// (g_out = y > 0 ? g : 0; y = NULL: no mask, g_out = NULL: not written), per-block column sums for the bias gradient
+// (part[blk][0][c], the layout bgnn_reduce_partials reads) and max|g_out| folded into *amax.
+// C4 = C / 4 threads per row (a power of two dividing 256), 256 / C4 rows per block step; the
+// column sums are reduced over the block's threads in a fixed order.
+constexpr int kPrepBlocks = 512;
+
+__global__ __launch_bounds__(256) void k_linear_bwd_prep(const float4* __restrict__ g, const float4* __restrict__ y,
+                                                         int64_t N, int C4, float4* __restrict__ gout,
+                                                         float* __restrict__ part, uint32_t* __restrict__ amax) {
+    __shared__ float4 red[256];
+    const int t = threadIdx.x;
+    const int rpi = 256 / C4;
+    const int c4 = t % C4;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    uint32_t m = 0;
+    // UR rows per iteration with their loads issued together (one load per row in flight left
+    // this pass latency-bound on tall inputs: EA_GNN's node-level [N, 512] gradients)
+    constexpr int UR = 4;
+    const int64_t stride = (int64_t)gridDim.x * rpi;
+    for (int64_t r0 = (int64_t)blockIdx.x * rpi + t / C4; r0 < N; r0 += UR * stride) {
+        float4 vv[UR], qq[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int64_t r = r0 + u * stride;
+            vv[u] = r < N ? g[r * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (y) qq[u] = r < N ? y[r * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int64_t r = r0 + u * stride;
+            float4 v = vv[u];
+            if (y) {
+                const float4 q = qq[u];
+                v.x = q.x > 0.f ? v.x : 0.f;
+                v.y = q.y > 0.f ? v.y : 0.f;
+                v.z = q.z > 0.f ? v.z : 0.f;
+                v.w = q.w > 0.f ? v.w : 0.f;
+            }
+            if (gout && r < N) gout[r * C4 + c4] = v;
+            acc.x += v.x;
+            acc.y += v.y;
+            acc.z += v.z;
+            acc.w += v.w;
+            m = max(m, max(max(__float_as_uint(v.x) & 0x7fffffffu, __float_as_uint(v.y) & 0x7fffffffu),
+                           max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu)));
+        }
+    }
+    red[t] = acc;
+    block_amax(amax, m);   // (its barrier also orders red)
+    if (t < C4) {
+        float4 s4 = red[t];
+        for (int k = 1; k < rpi; ++k) {
+            const float4 q = red[t + k * C4];
+            s4.x += q.x;
+            s4.y += q.y;
+            s4.z += q.z;
+            s4.w += q.w;
+        }
+        reinterpret_cast<float4*>(part + (int64_t)blockIdx.x * 2 * (4 * C4))[t] = s4;
+    }
+}
+
+// bf16 form (EA_GNN's bf16 configuration, bgnn.fused.LinearBf16Fn / bgnn.ea's gathered Linear):
+// g, y, g_out bf16 [N, C] (8 elements per 16-B access, C8 = C / 8 threads per row), column sums
+// in f32 (each bf16 value is exact in f32), no max|g| (the bf16 GEMMs need no operand scale).
+// Replaces torch's threshold_backward + sum(g, 0, dtype=float32): one pass instead of three.
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+
+__global__ __launch_bounds__(256) void k_linear_bwd_prep_bf16(const uint4* __restrict__ g, const uint4* __restrict__ y,
+                                                              int64_t N, int C8, uint4* __restrict__ gout,
+                                                              float* __restrict__ part) {
+    __shared__ float red[256][8];
+    const int t = threadIdx.x;
+    const int rpi = 256 / C8;
+    const int c8 = t % C8;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // UR rows per iteration, their loads issued together: one 16-B load per row and a grid of
+    // 512 blocks left a bias-only pass (no y) latency-bound at ~2 TB/s
+    constexpr int UR = 4;
+    const int64_t stride = (int64_t)gridDim.x * rpi;
+    for (int64_t r0 = (int64_t)blockIdx.x * rpi + t / C8; r0 < N; r0 += UR * stride) {
+        uint4 v[UR], q[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int64_t r = r0 + u * stride;
+            v[u] = r < N ? g[r * C8 + c8] : make_uint4(0u, 0u, 0u, 0u);
+            if (y) q[u] = r < N ? y[r * C8 + c8] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int64_t r = r0 + u * stride;
+            uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            if (y) {
+                const uint32_t qy[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t lo = bf16_lo(qy[k]) > 0.f ? 0x0000ffffu : 0u;
+                    const uint32_t hi = bf16_hi(qy[k]) > 0.f ? 0xffff0000u : 0u;
+                    w[k] &= lo | hi;
+                }
+                if (gout && r < N) gout[r * C8 + c8] = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                acc[2 * k] += bf16_lo(w[k]);
+                acc[2 * k + 1] += bf16_hi(w[k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) red[t][k] = acc[k];
+    __syncthreads();
+    if (t < C8) {
+        float s8[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s8[k] = red[t][k];
+        for (int q = 1; q < rpi; ++q)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s8[k] += red[t + q * C8][k];
+        float4* dst = reinterpret_cast<float4*>(part + (int64_t)blockIdx.x * 2 * (8 * C8)) + 2 * t;
+        dst[0] = make_float4(s8[0], s8[1], s8[2], s8[3]);
+        dst[1] = make_float4(s8[4], s8[5], s8[6], s8[7]);
+    }
+}
+
 }  // namespace bgnn
 
 using namespace bgnn;
@@ -488,5 +620,38 @@ extern "C" int bgnn_small_linear_bwd(const float* gy, const float* y, const floa
                            dx);
         BGNN_CHECK_LAUNCH();
     }
+    return BGNN_OK;
+}
+
+extern "C" int bgnn_linear_bwd_prep_bf16(const void* g, const void* y, int64_t N, int32_t C, void* g_out,
+                                         float* partial, void* stream) {
+    BGNN_REQUIRE(g && partial && N >= 0, "linear_bwd_prep_bf16: null pointer or negative size");
+    BGNN_REQUIRE(y == nullptr || g_out != nullptr, "linear_bwd_prep_bf16: a ReLU mask needs g_out");
+    BGNN_REQUIRE(C >= 8 && C <= 2048 && C % 8 == 0 && (256 % (C / 8)) == 0,
+                 "linear_bwd_prep_bf16: C = %d must be 8 * a power of two <= 2048", C);
+    BGNN_REQUIRE((((uintptr_t)g | (uintptr_t)(g_out ? g_out : g) | (uintptr_t)partial | (uintptr_t)(y ? y : g)) & 15) == 0,
+                 "linear_bwd_prep_bf16: pointers must be 16-B aligned");
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_linear_bwd_prep_bf16, dim3(kPrepBlocks), dim3(256), 0, s, reinterpret_cast<const uint4*>(g),
+                       reinterpret_cast<const uint4*>(y), N, C / 8, reinterpret_cast<uint4*>(g_out), partial);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
+
+extern "C" int32_t bgnn_linear_bwd_prep_slots(void) { return kPrepBlocks; }
+
+extern "C" int bgnn_linear_bwd_prep(const float* g, const float* y, int64_t N, int32_t C, float* g_out,
+                                    float* partial, float* amax, void* stream) {
+    BGNN_REQUIRE(g && partial && amax && N >= 0, "linear_bwd_prep: null pointer or negative size");
+    BGNN_REQUIRE(y == nullptr || g_out != nullptr, "linear_bwd_prep: a ReLU mask needs g_out");
+    BGNN_REQUIRE(C >= 4 && C <= 1024 && C % 4 == 0 && (256 % (C / 4)) == 0,
+                 "linear_bwd_prep: C = %d must be 4 * a power of two <= 1024", C);
+    BGNN_REQUIRE((((uintptr_t)g | (uintptr_t)(g_out ? g_out : g) | (uintptr_t)partial | (uintptr_t)(y ? y : g)) & 15) == 0,
+                 "linear_bwd_prep: pointers must be 16-B aligned");
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_linear_bwd_prep, dim3(kPrepBlocks), dim3(256), 0, s, reinterpret_cast<const float4*>(g),
+                       reinterpret_cast<const float4*>(y), N, C / 4, reinterpret_cast<float4*>(g_out), partial,
+                       reinterpret_cast<uint32_t*>(amax));
+    BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }

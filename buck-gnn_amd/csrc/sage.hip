@@ -1,11 +1,18 @@
-// Fused element-wise / row-wise pieces of the GraphSAGE layer loop
-// (Models/BuckGNN.py:430-444):  BatchNorm1d(train) -> ReLU -> skip -> Dropout,
-// and the backward of BatchNorm + the L2 normalize of SAGEConv(normalize=True).
+// The f32 GraphSAGE layer loop around the aggregation (Models/BuckGNN.py:430-444):
+//   forward   x_next = Dropout(ReLU(BatchNorm1d(o)) + skip * x_prev): k_sage_apply (flat),
+//             k_sage_apply_rows (row-blocked, with the range partials of x_next) and
+//             k_sage_apply_pool (with the segment pool of x_next), over one element body
+//             (apply_vec) and one argument struct filled and validated in one place (apply_args);
+//   backward  of BatchNorm(train) and of SAGEConv's L2 normalize: the column sums
+//             (k_sage_bwd_stats), then one wave per row (k_sage_bwd_rows; bgnn_l2norm_bwd is its
+//             RELU = false form), launched from one place (launch_bwd_rows);
+//   slots     every per-block partial [n_slots, 2, H] of these passes, of bn.hip and of the Linear
+//             backward prep (mlp.hip) is summed by k_reduce_slots, in f64 and in a fixed order, so
+//             results do not depend on scheduling; its BatchNorm form ends in bn_finalize.
 //
-// All kernels stream [N, H] fp32 rows with 16-B (float4) accesses. Reductions
-// over N (BatchNorm statistics, bias gradient) are per-block partial sums over
-// contiguous row ranges, reduced afterwards in fp64 in a fixed order, so results
-// do not depend on scheduling.
+// All kernels stream [N, H] fp32 rows with 16-B (float4) accesses.
+#include <type_traits>
+
 #include "common.h"
 #include "ranges.h"
 #include "seg_common.h"
@@ -13,118 +20,64 @@
 namespace bgnn {
 
 // ---------------------------------------------------------------------------
-// Stage 1 of every partial-slot reduction: [n_slots, 2H] -> kGroups group sums,
-// written IN PLACE into the first slot of each group's range (a thread reads its
-// whole column range before writing that column, and no other thread touches it).
-// Coalesced: a block covers 256 consecutive of the 2H columns for one group.
-constexpr int kGroups = 16;
+// What k_reduce_slots does with a channel's two slot sums. MODE 0 (SlotSums): out0 / out1 (either
+// may be NULL) = the sums, or += with accumulate. MODE 1 (BnParams): bn_finalize.
+struct SlotSums {
+    float* out0;
+    float* out1;
+    int accumulate;
+};
 
-__global__ __launch_bounds__(256) void k_slots_stage1(float* __restrict__ part, int n_slots, int W, int per) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    const int g = blockIdx.y;
-    if (c >= W) return;
-    const int s0 = g * per, s1 = min(n_slots, s0 + per);
-    if (s0 >= s1) return;
-    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int s = s0;
-    for (; s + 8 <= s1; s += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] += part[(int64_t)(s + u) * W + c];
-    }
-    for (; s < s1; ++s) acc[0] += part[(int64_t)s * W + c];
-    part[(int64_t)s0 * W + c] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-}
+struct BnParams {
+    int64_t count;         // rows behind the sums
+    const float* kshift;   // NULL, or the per-channel shift k the sums were taken about
+    const float* gamma;    // NULL: 1
+    const float* beta;     // NULL: 0
+    float eps, momentum;
+    float* rmean;          // running statistics, updated when both are set and momentum > 0
+    float* rvar;
+    float* mean;
+    float* invstd;
+    float* scale;
+    float* shift;
+};
 
-// Launch stage 1; returns the slot stride the stage-2 kernels must use.
-inline int slots_stage1(float* part, int n_slots, int H, hipStream_t s) {
-    if (n_slots <= kGroups) return 1;
-    const int per = (n_slots + kGroups - 1) / kGroups;
-    hipLaunchKernelGGL(k_slots_stage1, dim3((2 * H + 255) / 256, kGroups), dim3(256), 0, s, part, n_slots, 2 * H,
-                       per);
-    return per;
-}
-
-// ---------------------------------------------------------------------------
-// Reduce [n_slots, 2, H] partials (slots taken every `stride`); one thread per (channel, slot-phase).
-__global__ __launch_bounds__(256) void k_reduce_partials(const float* __restrict__ part, int n_slots, int stride,
-                                                         int H, float* __restrict__ out0, float* __restrict__ out1,
-                                                         int accumulate) {
-    __shared__ double red[4][2][64];
-    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    double s0 = 0.0, s1 = 0.0;
-    if (c < H)
-        for (int sl = ph * stride; sl < n_slots; sl += 4 * stride) {
-            s0 += (double)part[(int64_t)sl * 2 * H + c];
-            s1 += (double)part[(int64_t)sl * 2 * H + H + c];
-        }
-    red[ph][0][cl] = s0;
-    red[ph][1][cl] = s1;
-    __syncthreads();
-    if (ph == 0 && c < H) {
-        s0 = (red[0][0][cl] + red[1][0][cl]) + (red[2][0][cl] + red[3][0][cl]);
-        s1 = (red[0][1][cl] + red[1][1][cl]) + (red[2][1][cl] + red[3][1][cl]);
-        if (out0) out0[c] = accumulate ? out0[c] + (float)s0 : (float)s0;
-        if (out1) out1[c] = accumulate ? out1[c] + (float)s1 : (float)s1;
+// BatchNorm1d finalize of channel c (train mode, torch semantics), in f64 from s0 = sum (x - k) and
+// s1 = sum (x - k)^2 over `count` rows (k = kshift[c], or 0 without kshift):
+//   mean = k + s0 / n,  var = max(s1 / n - (s0 / n)^2, 0)  (biased: the normalisation's),
+//   invstd = 1 / sqrt(var + eps),  scale = gamma invstd,  shift = beta - mean scale,
+//   running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the
+//   unbiased var n / (n - 1) (var itself when n = 1).
+// (Every input is read before the first store: the struct's pointers carry no __restrict__.)
+__device__ __forceinline__ void bn_finalize(const BnParams& P, int c, double s0, double s1) {
+    const double k = P.kshift ? (double)P.kshift[c] : 0.0;
+    const float g = P.gamma ? P.gamma[c] : 1.f;
+    const float b = P.beta ? P.beta[c] : 0.f;
+    const bool running = P.rmean && P.rvar && P.momentum > 0.f;
+    const double rm = running ? (double)P.rmean[c] : 0.0, rv = running ? (double)P.rvar[c] : 0.0;
+    const double n = (double)P.count;
+    const double mu0 = s0 / n;
+    double var = s1 / n - mu0 * mu0;
+    if (var < 0.0) var = 0.0;
+    const double mu = P.kshift ? k + mu0 : mu0;
+    const double is = 1.0 / sqrt(var + (double)P.eps);
+    P.mean[c] = (float)mu;
+    P.invstd[c] = (float)is;
+    P.scale[c] = (float)((double)g * is);
+    P.shift[c] = (float)((double)b - mu * (double)g * is);
+    if (running) {
+        const double unb = P.count > 1 ? var * n / (n - 1.0) : var;
+        P.rmean[c] = (float)((1.0 - P.momentum) * rm + P.momentum * mu);
+        P.rvar[c] = (float)((1.0 - P.momentum) * rv + P.momentum * unb);
     }
 }
 
-// BatchNorm1d finalize (train mode), torch semantics: biased var for
-// normalisation, unbiased var for running_var, momentum update.
-__global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ part, int n_slots, int stride, int H,
-                                                     int64_t count, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, float eps, float momentum,
-                                                     float* __restrict__ rmean, float* __restrict__ rvar,
-                                                     float* __restrict__ mean, float* __restrict__ invstd,
-                                                     float* __restrict__ scale, float* __restrict__ shift) {
-    __shared__ double red[4][2][64];
-    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    double s0 = 0.0, s1 = 0.0;
-    if (c < H)
-        for (int sl = ph * stride; sl < n_slots; sl += 4 * stride) {
-            s0 += (double)part[(int64_t)sl * 2 * H + c];
-            s1 += (double)part[(int64_t)sl * 2 * H + H + c];
-        }
-    red[ph][0][cl] = s0;
-    red[ph][1][cl] = s1;
-    __syncthreads();
-    if (ph == 0 && c < H) {
-        s0 = (red[0][0][cl] + red[1][0][cl]) + (red[2][0][cl] + red[3][0][cl]);
-        s1 = (red[0][1][cl] + red[1][1][cl]) + (red[2][1][cl] + red[3][1][cl]);
-        const double n = (double)count;
-        const double mu = s0 / n;
-        double var = s1 / n - mu * mu;
-        if (var < 0.0) var = 0.0;
-        const double is = 1.0 / sqrt(var + (double)eps);
-        const float g = gamma ? gamma[c] : 1.f;
-        const float b = beta ? beta[c] : 0.f;
-        mean[c] = (float)mu;
-        invstd[c] = (float)is;
-        scale[c] = (float)((double)g * is);
-        shift[c] = (float)((double)b - mu * (double)g * is);
-        if (rmean && rvar && momentum > 0.f) {
-            const double unb = count > 1 ? var * n / (n - 1.0) : var;
-            rmean[c] = (float)((1.0 - momentum) * (double)rmean[c] + momentum * mu);
-            rvar[c] = (float)((1.0 - momentum) * (double)rvar[c] + momentum * unb);
-        }
-    }
-}
-
-// One-launch reduction of [n_slots, 2, H] partial slots (round 3; replaces k_slots_stage1 + the
-// final kernel, one launch fewer per reduction): a block owns 8 channels, its 256 threads are
-// 8 channels x 32 slot phases; each thread sums its slots ph, ph + 32, ... of both halves in f64
-// (eight loads in flight), then a fixed f64 tree over the 32 phases. MODE 0: out0 / out1 (=, or +=
-// with accumulate); MODE 1: the BatchNorm finalize of k_bn_finalize on (sum, sum of squares).
+// The reduction of [n_slots, 2, H] partial slots, one launch: a block owns 8 channels, its 256
+// threads are 8 channels x 32 slot phases; each thread sums its slots ph, ph + 32, ... of both
+// halves in f64 (eight loads in flight), then a fixed f64 tree over the 32 phases.
 template <int MODE>
 __global__ __launch_bounds__(256) void k_reduce_slots(const float* __restrict__ part, int n_slots, int H,
-                                                      float* __restrict__ out0, float* __restrict__ out1,
-                                                      int accumulate, int64_t count, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, float eps, float momentum,
-                                                      float* __restrict__ rmean, float* __restrict__ rvar,
-                                                      float* __restrict__ mean, float* __restrict__ invstd,
-                                                      float* __restrict__ scale, float* __restrict__ shift,
-                                                      const float* __restrict__ kshift) {
+                                                      std::conditional_t<MODE == 0, SlotSums, BnParams> A) {
     constexpr int CPB = 8, NPH = 256 / CPB;   // channels per block, slot phases
     __shared__ double red[2][NPH][CPB];
     const int cl = threadIdx.x % CPB, ph = threadIdx.x / CPB;
@@ -165,32 +118,20 @@ __global__ __launch_bounds__(256) void k_reduce_slots(const float* __restrict__ 
     s0 = red[0][0][cl];
     s1 = red[1][0][cl];
     if constexpr (MODE == 0) {
-        if (out0) out0[c] = accumulate ? out0[c] + (float)s0 : (float)s0;
-        if (out1) out1[c] = accumulate ? out1[c] + (float)s1 : (float)s1;
+        if (A.out0) A.out0[c] = A.accumulate ? A.out0[c] + (float)s0 : (float)s0;
+        if (A.out1) A.out1[c] = A.accumulate ? A.out1[c] + (float)s1 : (float)s1;
     } else {
-        // (kshift: the partials are sums of x - k and (x - k)^2, mean = k + their mean)
-        const double n = (double)count;
-        const double mu0 = s0 / n;
-        double var = s1 / n - mu0 * mu0;
-        if (var < 0.0) var = 0.0;
-        const double mu = kshift ? (double)kshift[c] + mu0 : mu0;
-        const double is = 1.0 / sqrt(var + (double)eps);
-        const float g = gamma ? gamma[c] : 1.f;
-        const float b = beta ? beta[c] : 0.f;
-        mean[c] = (float)mu;
-        invstd[c] = (float)is;
-        scale[c] = (float)((double)g * is);
-        shift[c] = (float)((double)b - mu * (double)g * is);
-        if (rmean && rvar && momentum > 0.f) {
-            const double unb = count > 1 ? var * n / (n - 1.0) : var;
-            rmean[c] = (float)((1.0 - momentum) * (double)rmean[c] + momentum * mu);
-            rvar[c] = (float)((1.0 - momentum) * (double)rvar[c] + momentum * unb);
-        }
+        bn_finalize(A, c, s0, s1);
     }
 }
 
-// one-launch reductions (k_reduce_slots) instead of stage 1 + final kernel (A/B switch)
-static int g_one_pass_reduce = 1;
+template <int MODE>
+int reduce_slots(const float* part, int n_slots, int H, const std::conditional_t<MODE == 0, SlotSums, BnParams>& A,
+                 void* stream) {
+    hipLaunchKernelGGL(k_reduce_slots<MODE>, dim3((H + 7) / 8), dim3(256), 0, as_stream(stream), part, n_slots, H, A);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
 
 __global__ void k_bn_eval(int H, const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                           const float* __restrict__ rmean, const float* __restrict__ rvar,
@@ -205,18 +146,20 @@ __global__ void k_bn_eval(int H, const float* __restrict__ gamma, const float* _
 }
 
 // ---------------------------------------------------------------------------
-// Fold a thread's running max |value| (f32 bits) into *amax: block max over 256 threads,
-// then one atomic per block. Must be reached by every thread of the block.
-__device__ __forceinline__ void block_amax(uint32_t* amax, uint32_t m) {
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, kWave));
-    __shared__ uint32_t red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (m) atomicMax(amax, m);
-    }
-}
+// The arguments the three forms of the apply pass share (filled by apply_args).
+struct ApplyArgs {
+    const float* o;
+    const float* scale;   // NULL (with shift): no BatchNorm
+    const float* shift;
+    const float* xprev;
+    uint32_t thr;         // dropout (common.h Dropout)
+    float inv_keep;
+    uint64_t seed;
+    int32_t H, nt;        // nt: non-temporal x_next stores
+    float* xn;
+    uint32_t* amax;       // NULL, or where max |x_next| is folded
+    int32_t skip;
+};
 
 // The element expression of x_next for one float4: y = o on entry, x_next on return;
 // drop(relu(o*scale+shift) + skip*x_prev), i = the float4's index row * H/4 + c4 (the dropout hash's
@@ -240,13 +183,27 @@ __device__ __forceinline__ void x_next4(float (&y)[4], bool bn, const float4& sc
     }
 }
 
-// x_next = drop(relu(o*scale+shift) + skip*x_prev). Grid-stride over float4s.
-__global__ __launch_bounds__(256) void k_sage_apply(const float4* __restrict__ o, const float* __restrict__ scale,
-                                                    const float* __restrict__ shift,
-                                                    const float4* __restrict__ xprev, int skip, uint32_t thr,
-                                                    float inv_keep, uint64_t seed, int64_t n4, int H4,
-                                                    float4* __restrict__ xn, uint32_t* __restrict__ amax, int nt,
-                                                    int rev) {
+// One float4 of the apply pass once its inputs are loaded (ov = o's float4 i, p = x_prev's when
+// skip): y = x_next4; a kept vector is stored (when `store`) and |y| folded into the running max m.
+__device__ __forceinline__ void apply_vec(const ApplyArgs& A, bool skip, const float4& ov, const float4& p,
+                                          const float4& sc, const float4& sh, int64_t i, bool keep, bool store,
+                                          float (&y)[4], uint32_t& m) {
+    y[0] = ov.x; y[1] = ov.y; y[2] = ov.z; y[3] = ov.w;
+    x_next4(y, A.scale != nullptr, sc, sh, skip, p, A.thr, A.inv_keep, A.seed, (uint64_t)i);
+    if (!keep) return;
+    if (store) store4(A.xn + 4 * i, y[0], y[1], y[2], y[3], A.nt);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
+}
+
+// x_prev's float4 i of a skip layer, zeros otherwise
+__device__ __forceinline__ float4 load_xprev(const ApplyArgs& A, int64_t i) {
+    return A.skip ? reinterpret_cast<const float4*>(A.xprev)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// x_next = drop(relu(o*scale+shift) + skip*x_prev). Grid-stride over the n4 = n_rows H / 4 float4s.
+__global__ __launch_bounds__(256) void k_sage_apply(ApplyArgs A, int64_t n4, int rev) {
+    const int H4 = A.H / 4;
     uint32_t m = 0;
     // rev = 1 (grid a multiple of 8): block b sweeps the eighth (b & 7) of the rows from its last
     // element down, so each eighth starts on the rows the aggregation (which sweeps the same
@@ -262,22 +219,17 @@ __global__ __launch_bounds__(256) void k_sage_apply(const float4* __restrict__ o
     }
     for (int64_t q = i0; q < hi - lo; q += st) {
         const int64_t i = rev ? hi - 1 - q : q;
+        const float4 ov = reinterpret_cast<const float4*>(A.o)[i];   // (issued ahead of the 64-bit i % H4)
         const int c = (int)(i % H4) * 4;
-        float4 v = o[i];
-        float y[4] = {v.x, v.y, v.z, v.w};
         float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (scale) {
-            sc = *reinterpret_cast<const float4*>(scale + c);
-            sh = *reinterpret_cast<const float4*>(shift + c);
+        if (A.scale) {
+            sc = *reinterpret_cast<const float4*>(A.scale + c);
+            sh = *reinterpret_cast<const float4*>(A.shift + c);
         }
-        if (skip) p = xprev[i];
-        x_next4(y, scale != nullptr, sc, sh, skip != 0, p, thr, inv_keep, seed, (uint64_t)i);
-        store4(reinterpret_cast<float*>(xn + i), y[0], y[1], y[2], y[3], nt);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
+        float y[4];
+        apply_vec(A, A.skip != 0, ov, load_xprev(A, i), sc, sh, i, true, true, y, m);
     }
-    if (amax) block_amax(amax, m);
+    if (A.amax) block_amax(A.amax, m);
 }
 
 // Row-blocked form of k_sage_apply with the range partials of x_next (bgnn_sage_apply given a
@@ -290,12 +242,7 @@ __global__ __launch_bounds__(256) void k_sage_apply(const float4* __restrict__ o
 // slot (BlockRanges; the slot is wave-uniform, so no register array is indexed); the 4 waves' sums
 // are added in wave order into rpart[lb][slot][H] (every slot written, 0 when unused).
 template <int NV>
-__global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict__ o, const float* __restrict__ scale,
-                                                         const float* __restrict__ shift,
-                                                         const float* __restrict__ xprev, int skip, uint32_t thr,
-                                                         float inv_keep, uint64_t seed, int64_t n_rows, int H,
-                                                         int64_t rpb, float* __restrict__ xn,
-                                                         uint32_t* __restrict__ amax, int nt,
+__global__ __launch_bounds__(256) void k_sage_apply_rows(ApplyArgs A, int64_t n_rows, int64_t rpb,
                                                          const int32_t* __restrict__ ranges,
                                                          float* __restrict__ rpart) {
     const int lane = threadIdx.x & 63;
@@ -303,7 +250,7 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
     const int lb = xcd_remap_rev(blockIdx.x, gridDim.x);
     const int64_t r0 = (int64_t)lb * rpb;
     const int64_t r1 = min(n_rows, r0 + rpb);
-    const int H4 = H / 4;
+    const int H = A.H, H4 = H / 4;
     BlockRanges br;
     br.load(ranges, r0, r1);
     __shared__ float4 racc[4][kRangeSlots][128];
@@ -315,8 +262,8 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
         c4[v] = lane + 64 * v;
         cok[v] = c4[v] < H4;
         const int c = cok[v] ? 4 * c4[v] : 0;
-        sc[v] = scale ? *reinterpret_cast<const float4*>(scale + c) : make_float4(1.f, 1.f, 1.f, 1.f);
-        sh[v] = shift ? *reinterpret_cast<const float4*>(shift + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        sc[v] = A.scale ? *reinterpret_cast<const float4*>(A.scale + c) : make_float4(1.f, 1.f, 1.f, 1.f);
+        sh[v] = A.shift ? *reinterpret_cast<const float4*>(A.shift + c) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int q = 0; q < kRangeSlots; ++q)
             if (cok[v]) racc[wave][q][c4[v]] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -328,14 +275,9 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
         for (int v = 0; v < NV; ++v) {
             if (!cok[v]) continue;
             const int64_t i = r * H4 + c4[v];
-            const float4 ov = reinterpret_cast<const float4*>(o)[i];
-            float y[4] = {ov.x, ov.y, ov.z, ov.w};
-            float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (skip) p = reinterpret_cast<const float4*>(xprev)[i];
-            x_next4(y, scale != nullptr, sc[v], sh[v], skip != 0, p, thr, inv_keep, seed, (uint64_t)i);
-            store4(xn + 4 * i, y[0], y[1], y[2], y[3], nt);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
+            const float4 ov = reinterpret_cast<const float4*>(A.o)[i];
+            float y[4];
+            apply_vec(A, A.skip != 0, ov, load_xprev(A, i), sc[v], sh[v], i, true, true, y, m);
             if (sl >= 0) {
                 float4 t = racc[wave][sl][c4[v]];
                 t.x += y[0]; t.y += y[1]; t.z += y[2]; t.w += y[3];
@@ -349,7 +291,7 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
         row(r - 4);
     }
     if (r >= r0) row(r);
-    if (amax) block_amax(amax, m);
+    if (A.amax) block_amax(A.amax, m);
     __syncthreads();
     float4* dst = reinterpret_cast<float4*>(rpart + (int64_t)lb * kRangeSlots * H);
     for (int c = threadIdx.x; c < kRangeSlots * H4; c += 256) {
@@ -378,17 +320,7 @@ __global__ __launch_bounds__(256) void k_sage_apply_rows(const float* __restrict
 // added one by one in CSR order with a rounded add (__fadd_rn: no contraction with the dropout
 // scale), so the sums have the bits of bgnn_spmm_fwd over the stored rows. x_next (optional) is
 // stored on the way: every row lies in exactly one segment.
-struct ApplyPoolArgs {
-    const float* o;
-    const float* scale;
-    const float* shift;
-    const float* xprev;
-    uint32_t thr;
-    float inv_keep;
-    uint64_t seed;
-    int32_t H, nt;
-    float* xn;
-    uint32_t* amax;
+struct ApplyPoolArgs : ApplyArgs {   // (skip is the kernel's template argument; xn may be NULL)
     const int32_t* rowptr;
     const int32_t* col;
     const int32_t* heavy_row;
@@ -421,14 +353,9 @@ __device__ __forceinline__ void apply_pool_batch(const ApplyPoolArgs& A, float (
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const bool ok = cok && u < nvalid;
-        float y[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w};
-        x_next4(y, A.scale != nullptr, sc, sh, SKIP, SKIP ? pv[u] : make_float4(0.f, 0.f, 0.f, 0.f), A.thr,
-                A.inv_keep, A.seed, (uint64_t)i[u]);
-        if (ok) {
-            if (A.xn) store4(A.xn + 4 * i[u], y[0], y[1], y[2], y[3], A.nt);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) m = max(m, __float_as_uint(y[k]) & 0x7fffffffu);
-        }
+        float y[4];
+        apply_vec(A, SKIP, ov[u], SKIP ? pv[u] : make_float4(0.f, 0.f, 0.f, 0.f), sc, sh, i[u], ok, A.xn != nullptr, y,
+                  m);
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], ok ? y[k] : 0.f);
     }
@@ -501,7 +428,6 @@ __global__ __launch_bounds__(256) void k_sage_bwd_stats(const float* __restrict_
                                                         const float* __restrict__ invstd, uint32_t thr,
                                                         float inv_keep, uint64_t seed, int64_t n_rows, int H,
                                                         int64_t rows_per_block, float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float red[2][2][512];
     const int H4 = H / 4;
     const int rpi = 256 / H4;                 // rows per iteration
     const int t = threadIdx.x;
@@ -536,29 +462,16 @@ __global__ __launch_bounds__(256) void k_sage_bwd_stats(const float* __restrict_
             }
         }
     }
-    // reduce over row phases (rpi ≤ 2 for H = 512; general rpi via loop)
-    __shared__ __attribute__((aligned(16))) float red_all[256][8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { red_all[t][k] = s0[k]; red_all[t][4 + k] = s1[k]; }
-    __syncthreads();
-    (void)red;
-    if (t < H4) {
-        float a0[4] = {0, 0, 0, 0}, a1[4] = {0, 0, 0, 0};
-        for (int q = 0; q < rpi; ++q)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                a0[k] += red_all[q * H4 + t][k];
-                a1[k] += red_all[q * H4 + t][4 + k];
-            }
-        float* dst = part + (int64_t)lb * 2 * H;
-        *reinterpret_cast<float4*>(dst + c) = make_float4(a0[0], a0[1], a0[2], a0[3]);
-        *reinterpret_cast<float4*>(dst + H + c) = make_float4(a1[0], a1[1], a1[2], a1[3]);
-    }
+    block_col_partials(s0, s1, H, part + (int64_t)lb * 2 * H);   // (over the row phases: rpi <= 2 at H = 512)
 }
 
 // Backward pass 2: one wave per row (H <= 512, NV float4 per lane). RELU = false: the layer
 // is the bare SAGEConv(normalize=True) of the per-op path (g is dL/do; no ReLU mask, no BN,
 // no dropout), i.e. only the L2-normalize backward.
+// The parameters stay positional, spread from BwdRowsArgs in one place (launch_bwd_rows): the
+// pointers of an argument struct passed by value carry no __restrict__, and without it the
+// wave-uniform loads in the row loop (g_rows[r], nrm[r], the rowptr pairs) are no longer scalar
+// loads but vector loads whose s_waitcnt vmcnt(0) also waits for the row prefetched one ahead.
 template <int NV, bool RELU = true, bool RANGES = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_sage_bwd_rows(
     const float* __restrict__ g, const int64_t* __restrict__ g_rows, const float* __restrict__ o,
@@ -761,8 +674,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static int g_rows_nt = 0;
 void set_rows_nt(int on) { g_rows_nt = on ? 1 : 0; }
 int rows_nt() { return g_rows_nt; }
@@ -770,197 +681,93 @@ static int g_rows_rev = 1;   // bit 0 on: bwd_rows 107.5 -> 92.9 us in the cfg2 
 void set_rows_rev(int on) { g_rows_rev = on & 15; }
 int rows_rev() { return g_rows_rev; }
 
+// The checks and the arguments that bgnn_sage_apply and bgnn_sage_apply_pool share; `name` is the
+// entry point's, the prefix of its messages. need_xn: x_next must be set (the pool form may drop it).
+static int apply_args(ApplyArgs& A, const char* name, const float* o, const float* scale, const float* shift,
+                      const float* x_prev, int32_t skip, float p, uint64_t seed, int64_t n_rows, int32_t H,
+                      float* x_next, float* amax, bool need_xn) {
+    BGNN_REQUIRE(H > 0 && H % 4 == 0, "%s: H must be a multiple of 4", name);
+    BGNN_REQUIRE(n_rows >= 0, "%s: negative n_rows", name);
+    BGNN_REQUIRE(n_rows == 0 || (o && (x_next || !need_xn)), "%s: null o%s", name, need_xn ? " / x_next" : "");
+    BGNN_REQUIRE(p >= 0.f && p < 1.f, "%s: dropout p must be in [0, 1)", name);
+    BGNN_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale/shift must both be set or NULL", name);
+    BGNN_REQUIRE(!skip || x_prev, "%s: skip requires x_prev", name);
+    BGNN_REQUIRE(aligned16(o) && aligned16(x_next) && (!x_prev || aligned16(x_prev)) &&
+                     (!scale || (aligned16(scale) && aligned16(shift))),
+                 "%s: pointers must be 16-byte aligned", name);
+    const Dropout d = dropout_of(p);
+    A.o = o; A.scale = scale; A.shift = shift; A.xprev = x_prev;
+    A.thr = d.thr;
+    A.inv_keep = d.inv_keep;
+    A.seed = seed;
+    A.H = H;
+    A.nt = rows_nt();
+    A.xn = x_next;
+    A.amax = reinterpret_cast<uint32_t*>(amax);
+    A.skip = skip;
+    return BGNN_OK;
+}
+
+// bgnn_sage_bwd_rows' arguments as its two callers fill them (include/bgnn.h; part = partial_db,
+// rw_rowptr / rpart = range_w_rowptr / range_partial). Zero: no BatchNorm, no dropout (inv_keep
+// unread), no skip, no row weights, no ranges.
+struct BwdRowsArgs {
+    const float* g;
+    const int64_t* g_rows;
+    const float* o;
+    const float* nrm;
+    const float* scale;
+    const float* shift;
+    const float* gamma;
+    const float* mean;
+    const float* invstd;
+    const float* sum_g2;
+    const float* sum_g2xhat;
+    Dropout drop;
+    uint64_t seed;
+    int32_t skip;
+    int64_t n_rows;
+    int32_t H;
+    float* dh;
+    int64_t lddh;
+    float* gskip;
+    float* part;
+    float* amax;
+    const int32_t* w_rowptr;
+    int32_t w_mode;
+    const int32_t* ranges;
+    const int32_t* rw_rowptr;
+    float* rpart;
+};
+
+// The launch of k_sage_bwd_rows (bgnn_sage_bwd_rows; relu = false: bgnn_l2norm_bwd, which has no
+// ranges): the row partition, the store policy and the sweep direction, and the instantiation.
+static int launch_bwd_rows(const BwdRowsArgs& A, bool relu, void* stream) {
+    int64_t rpb = 0;
+    const int64_t blocks = rows_grid(A.n_rows, 4, &rpb);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), A.g, A.g_rows, A.o, A.nrm,
+                           A.scale, A.shift, A.gamma, A.mean, A.invstd, A.sum_g2, A.sum_g2xhat, A.drop.thr,
+                           A.drop.inv_keep, A.seed, A.skip, A.n_rows, A.H, rpb, A.dh, A.lddh, A.gskip, A.part,
+                           reinterpret_cast<uint32_t*>(A.amax), rows_nt(), A.w_rowptr, A.w_mode, rows_rev() & 1, A.ranges,
+                           A.rw_rowptr, A.rpart);
+    };
+    const bool wide = A.H > 256;   // two float4 per lane
+    if (!relu) wide ? launch(k_sage_bwd_rows<2, false>) : launch(k_sage_bwd_rows<1, false>);
+    else if (A.ranges) wide ? launch(k_sage_bwd_rows<2, true, true>) : launch(k_sage_bwd_rows<1, true, true>);
+    else wide ? launch(k_sage_bwd_rows<2>) : launch(k_sage_bwd_rows<1>);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
+
 }  // namespace bgnn
 
 using namespace bgnn;
 
-// ---------------------------------------------------------------------------
-// Output-gradient prep of a dense Linear (the encoder MLP's LinearFn.backward,
-// Models/BuckGNN.py:67-74) in one pass over g [N, C]: the fused ReLU's mask
-// (g_out = y > 0 ? g : 0; y = NULL: no mask, g_out = NULL: not written), per-block column sums for the bias gradient
-// (part[blk][0][c], the layout bgnn_reduce_partials reads) and max|g_out| folded into *amax.
-// C4 = C / 4 threads per row (a power of two dividing 256), 256 / C4 rows per block step; the
-// column sums are reduced over the block's threads in a fixed order.
-constexpr int kPrepBlocks = 512;
-
-__global__ __launch_bounds__(256) void k_linear_bwd_prep(const float4* __restrict__ g, const float4* __restrict__ y,
-                                                         int64_t N, int C4, float4* __restrict__ gout,
-                                                         float* __restrict__ part, uint32_t* __restrict__ amax) {
-    __shared__ float4 red[256];
-    const int t = threadIdx.x;
-    const int rpi = 256 / C4;
-    const int c4 = t % C4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    uint32_t m = 0;
-    // UR rows per iteration with their loads issued together (one load per row in flight left
-    // this pass latency-bound on tall inputs: EA_GNN's node-level [N, 512] gradients)
-    constexpr int UR = 4;
-    const int64_t stride = (int64_t)gridDim.x * rpi;
-    for (int64_t r0 = (int64_t)blockIdx.x * rpi + t / C4; r0 < N; r0 += UR * stride) {
-        float4 vv[UR], qq[UR];
-#pragma unroll
-        for (int u = 0; u < UR; ++u) {
-            const int64_t r = r0 + u * stride;
-            vv[u] = r < N ? g[r * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (y) qq[u] = r < N ? y[r * C4 + c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < UR; ++u) {
-            const int64_t r = r0 + u * stride;
-            float4 v = vv[u];
-            if (y) {
-                const float4 q = qq[u];
-                v.x = q.x > 0.f ? v.x : 0.f;
-                v.y = q.y > 0.f ? v.y : 0.f;
-                v.z = q.z > 0.f ? v.z : 0.f;
-                v.w = q.w > 0.f ? v.w : 0.f;
-            }
-            if (gout && r < N) gout[r * C4 + c4] = v;
-            acc.x += v.x;
-            acc.y += v.y;
-            acc.z += v.z;
-            acc.w += v.w;
-            m = max(m, max(max(__float_as_uint(v.x) & 0x7fffffffu, __float_as_uint(v.y) & 0x7fffffffu),
-                           max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu)));
-        }
-    }
-    red[t] = acc;
-    // one atomic per block (same-address atomics serialise in L2)
-    __shared__ uint32_t wmax[4];
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, kWave));
-    if ((t & 63) == 0) wmax[t >> 6] = m;
-    __syncthreads();
-    if (t == 0) {
-        m = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
-        if (m) atomicMax(amax, m);
-    }
-    if (t < C4) {
-        float4 s4 = red[t];
-        for (int k = 1; k < rpi; ++k) {
-            const float4 q = red[t + k * C4];
-            s4.x += q.x;
-            s4.y += q.y;
-            s4.z += q.z;
-            s4.w += q.w;
-        }
-        reinterpret_cast<float4*>(part + (int64_t)blockIdx.x * 2 * (4 * C4))[t] = s4;
-    }
-}
-
-// bf16 form (EA_GNN's bf16 configuration, bgnn.fused.LinearBf16Fn / bgnn.ea's gathered Linear):
-// g, y, g_out bf16 [N, C] (8 elements per 16-B access, C8 = C / 8 threads per row), column sums
-// in f32 (each bf16 value is exact in f32), no max|g| (the bf16 GEMMs need no operand scale).
-// Replaces torch's threshold_backward + sum(g, 0, dtype=float32): one pass instead of three.
-__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-
-__global__ __launch_bounds__(256) void k_linear_bwd_prep_bf16(const uint4* __restrict__ g, const uint4* __restrict__ y,
-                                                              int64_t N, int C8, uint4* __restrict__ gout,
-                                                              float* __restrict__ part) {
-    __shared__ float red[256][8];
-    const int t = threadIdx.x;
-    const int rpi = 256 / C8;
-    const int c8 = t % C8;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // UR rows per iteration, their loads issued together: one 16-B load per row and a grid of
-    // 512 blocks left a bias-only pass (no y) latency-bound at ~2 TB/s
-    constexpr int UR = 4;
-    const int64_t stride = (int64_t)gridDim.x * rpi;
-    for (int64_t r0 = (int64_t)blockIdx.x * rpi + t / C8; r0 < N; r0 += UR * stride) {
-        uint4 v[UR], q[UR];
-#pragma unroll
-        for (int u = 0; u < UR; ++u) {
-            const int64_t r = r0 + u * stride;
-            v[u] = r < N ? g[r * C8 + c8] : make_uint4(0u, 0u, 0u, 0u);
-            if (y) q[u] = r < N ? y[r * C8 + c8] : make_uint4(0u, 0u, 0u, 0u);
-        }
-#pragma unroll
-        for (int u = 0; u < UR; ++u) {
-            const int64_t r = r0 + u * stride;
-            uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            if (y) {
-                const uint32_t qy[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t lo = bf16_lo(qy[k]) > 0.f ? 0x0000ffffu : 0u;
-                    const uint32_t hi = bf16_hi(qy[k]) > 0.f ? 0xffff0000u : 0u;
-                    w[k] &= lo | hi;
-                }
-                if (gout && r < N) gout[r * C8 + c8] = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc[2 * k] += bf16_lo(w[k]);
-                acc[2 * k + 1] += bf16_hi(w[k]);
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) red[t][k] = acc[k];
-    __syncthreads();
-    if (t < C8) {
-        float s8[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s8[k] = red[t][k];
-        for (int q = 1; q < rpi; ++q)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s8[k] += red[t + q * C8][k];
-        float4* dst = reinterpret_cast<float4*>(part + (int64_t)blockIdx.x * 2 * (8 * C8)) + 2 * t;
-        dst[0] = make_float4(s8[0], s8[1], s8[2], s8[3]);
-        dst[1] = make_float4(s8[4], s8[5], s8[6], s8[7]);
-    }
-}
-
-extern "C" int bgnn_linear_bwd_prep_bf16(const void* g, const void* y, int64_t N, int32_t C, void* g_out,
-                                         float* partial, void* stream) {
-    BGNN_REQUIRE(g && partial && N >= 0, "linear_bwd_prep_bf16: null pointer or negative size");
-    BGNN_REQUIRE(y == nullptr || g_out != nullptr, "linear_bwd_prep_bf16: a ReLU mask needs g_out");
-    BGNN_REQUIRE(C >= 8 && C <= 2048 && C % 8 == 0 && (256 % (C / 8)) == 0,
-                 "linear_bwd_prep_bf16: C = %d must be 8 * a power of two <= 2048", C);
-    BGNN_REQUIRE((((uintptr_t)g | (uintptr_t)(g_out ? g_out : g) | (uintptr_t)partial | (uintptr_t)(y ? y : g)) & 15) == 0,
-                 "linear_bwd_prep_bf16: pointers must be 16-B aligned");
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_linear_bwd_prep_bf16, dim3(kPrepBlocks), dim3(256), 0, s, reinterpret_cast<const uint4*>(g),
-                       reinterpret_cast<const uint4*>(y), N, C / 8, reinterpret_cast<uint4*>(g_out), partial);
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
-}
-
-extern "C" int32_t bgnn_linear_bwd_prep_slots(void) { return kPrepBlocks; }
-
-extern "C" int bgnn_linear_bwd_prep(const float* g, const float* y, int64_t N, int32_t C, float* g_out,
-                                    float* partial, float* amax, void* stream) {
-    BGNN_REQUIRE(g && partial && amax && N >= 0, "linear_bwd_prep: null pointer or negative size");
-    BGNN_REQUIRE(y == nullptr || g_out != nullptr, "linear_bwd_prep: a ReLU mask needs g_out");
-    BGNN_REQUIRE(C >= 4 && C <= 1024 && C % 4 == 0 && (256 % (C / 4)) == 0,
-                 "linear_bwd_prep: C = %d must be 4 * a power of two <= 1024", C);
-    BGNN_REQUIRE((((uintptr_t)g | (uintptr_t)(g_out ? g_out : g) | (uintptr_t)partial | (uintptr_t)(y ? y : g)) & 15) == 0,
-                 "linear_bwd_prep: pointers must be 16-B aligned");
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(k_linear_bwd_prep, dim3(kPrepBlocks), dim3(256), 0, s, reinterpret_cast<const float4*>(g),
-                       reinterpret_cast<const float4*>(y), N, C / 4, reinterpret_cast<float4*>(g_out), partial,
-                       reinterpret_cast<uint32_t*>(amax));
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
-}
-
 extern "C" int bgnn_reduce_partials(const float* partial, int32_t n_slots, int32_t H, float* out0, float* out1,
                                     int32_t accumulate, void* stream) {
     BGNN_REQUIRE(partial && H > 0 && n_slots >= 0, "reduce_partials: bad args");
-    hipStream_t s = as_stream(stream);
-    if (g_one_pass_reduce) {
-        hipLaunchKernelGGL(k_reduce_slots<0>, dim3((H + 7) / 8), dim3(256), 0, s, partial, n_slots, H, out0, out1,
-                           accumulate, (int64_t)0, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr);
-        BGNN_CHECK_LAUNCH();
-        return BGNN_OK;
-    }
-    const int stride = slots_stage1(const_cast<float*>(partial), n_slots, H, s);
-    BGNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_reduce_partials, dim3((H + 63) / 64), dim3(256), 0, s, partial, n_slots, stride, H, out0,
-                       out1, accumulate);
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
+    return reduce_slots<0>(partial, n_slots, H, SlotSums{out0, out1, accumulate}, stream);
 }
 
 extern "C" int bgnn_bn_finalize(const float* bn_partial, int32_t n_slots, int32_t H, int64_t count,
@@ -968,20 +775,10 @@ extern "C" int bgnn_bn_finalize(const float* bn_partial, int32_t n_slots, int32_
                                 float* running_mean, float* running_var, float* mean, float* invstd, float* scale,
                                 float* shift, void* stream) {
     BGNN_REQUIRE(bn_partial && H > 0 && count > 0 && mean && invstd && scale && shift, "bn_finalize: bad args");
-    hipStream_t s = as_stream(stream);
-    if (g_one_pass_reduce) {
-        hipLaunchKernelGGL(k_reduce_slots<1>, dim3((H + 7) / 8), dim3(256), 0, s, bn_partial, n_slots, H, nullptr,
-                           nullptr, 0, count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
-                           scale, shift, nullptr);
-        BGNN_CHECK_LAUNCH();
-        return BGNN_OK;
-    }
-    const int stride = slots_stage1(const_cast<float*>(bn_partial), n_slots, H, s);
-    BGNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_bn_finalize, dim3((H + 63) / 64), dim3(256), 0, s, bn_partial, n_slots, stride, H, count,
-                       gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, scale, shift);
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
+    return reduce_slots<1>(bn_partial, n_slots, H,
+                           BnParams{count, nullptr, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
+                                    scale, shift},
+                           stream);
 }
 
 extern "C" int bgnn_bn_finalize_shifted(const float* bn_partial, int32_t n_slots, int32_t H, int64_t count,
@@ -990,11 +787,10 @@ extern "C" int bgnn_bn_finalize_shifted(const float* bn_partial, int32_t n_slots
                                         float* invstd, float* scale, float* shift, void* stream) {
     BGNN_REQUIRE(bn_partial && kshift && H > 0 && count > 0 && mean && invstd && scale && shift,
                  "bn_finalize_shifted: bad args");
-    hipLaunchKernelGGL(k_reduce_slots<1>, dim3((H + 7) / 8), dim3(256), 0, as_stream(stream), bn_partial, n_slots, H,
-                       nullptr, nullptr, 0, count, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
-                       scale, shift, kshift);
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
+    return reduce_slots<1>(bn_partial, n_slots, H,
+                           BnParams{count, kshift, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
+                                    scale, shift},
+                           stream);
 }
 
 extern "C" int bgnn_bn_eval_coeffs(int32_t H, const float* gamma, const float* beta, float eps,
@@ -1011,44 +807,26 @@ extern "C" int bgnn_bn_eval_coeffs(int32_t H, const float* gamma, const float* b
 extern "C" int bgnn_sage_apply(const float* o, const float* scale, const float* shift, const float* x_prev,
                                int32_t skip, float p, uint64_t seed, int64_t n_rows, int32_t H, float* x_next,
                                float* amax, const int32_t* ranges, float* range_partial, void* stream) {
-    BGNN_REQUIRE(H > 0 && H % 4 == 0, "sage_apply: H must be a multiple of 4");
-    BGNN_REQUIRE(n_rows >= 0, "sage_apply: negative n_rows");
-    BGNN_REQUIRE(n_rows == 0 || (o && x_next), "sage_apply: null o / x_next");
-    BGNN_REQUIRE(p >= 0.f && p < 1.f, "sage_apply: dropout p must be in [0, 1)");
-    BGNN_REQUIRE((scale == nullptr) == (shift == nullptr), "sage_apply: scale/shift must both be set or NULL");
-    BGNN_REQUIRE(!skip || x_prev, "sage_apply: skip requires x_prev");
-    BGNN_REQUIRE(al16(o) && al16(x_next) && (!x_prev || al16(x_prev)) && (!scale || (al16(scale) && al16(shift))),
-                 "sage_apply: pointers must be 16-byte aligned");
-    BGNN_REQUIRE(!ranges || (range_partial && ((uintptr_t)range_partial & 15) == 0 && H <= 512),
+    ApplyArgs A{};
+    if (const int e = apply_args(A, "sage_apply", o, scale, shift, x_prev, skip, p, seed, n_rows, H, x_next, amax, true))
+        return e;
+    BGNN_REQUIRE(!ranges || (range_partial && aligned16(range_partial) && H <= 512),
                  "sage_apply: ranges need a 16-B aligned range_partial and H <= 512");
     if (n_rows == 0) return BGNN_OK;
     hipStream_t s = as_stream(stream);
     if (ranges) {   // row-blocked form with the range partials (the same x_next)
-        const uint32_t thr = dropout_threshold(p);
-        const float inv_keep = thr ? 1.f / (1.f - p) : 1.f;
         int64_t rpb = 0;
         const int64_t blocks = rows_slots_of(n_rows, &rpb);
-        if (H > 256)
-            hipLaunchKernelGGL(k_sage_apply_rows<2>, dim3((unsigned)blocks), dim3(256), 0, s, o, scale, shift, x_prev,
-                               skip, thr, inv_keep, seed, n_rows, H, rpb, x_next, reinterpret_cast<uint32_t*>(amax),
-                               rows_nt(), ranges, range_partial);
-        else
-            hipLaunchKernelGGL(k_sage_apply_rows<1>, dim3((unsigned)blocks), dim3(256), 0, s, o, scale, shift, x_prev,
-                               skip, thr, inv_keep, seed, n_rows, H, rpb, x_next, reinterpret_cast<uint32_t*>(amax),
-                               rows_nt(), ranges, range_partial);
-        BGNN_CHECK_LAUNCH();
-        return BGNN_OK;
+        hipLaunchKernelGGL(H > 256 ? k_sage_apply_rows<2> : k_sage_apply_rows<1>, dim3((unsigned)blocks), dim3(256), 0, s,
+                           A, n_rows, rpb, ranges, range_partial);
+    } else {
+        const int64_t n4 = n_rows * (H / 4);
+        int64_t blocks = (n4 + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        const int rev = (rows_rev() & 2) ? 1 : 0;
+        if (rev) blocks = (blocks + 7) / 8 * 8;
+        hipLaunchKernelGGL(k_sage_apply, dim3((unsigned)blocks), dim3(256), 0, s, A, n4, rev);
     }
-    const int64_t n4 = n_rows * (H / 4);
-    int64_t blocks = (n4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    const int rev = (rows_rev() & 2) ? 1 : 0;
-    if (rev) blocks = (blocks + 7) / 8 * 8;
-    const uint32_t thr = dropout_threshold(p);
-    const float inv_keep = thr ? 1.f / (1.f - p) : 1.f;
-    hipLaunchKernelGGL(k_sage_apply, dim3((unsigned)blocks), dim3(256), 0, s, (const float4*)o, scale, shift,
-                       (const float4*)x_prev, skip, thr, inv_keep, seed, n4, H / 4, (float4*)x_next,
-                       reinterpret_cast<uint32_t*>(amax), rows_nt(), rev);
     BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }
@@ -1057,14 +835,10 @@ extern "C" int bgnn_sage_apply_pool(const float* o, const float* scale, const fl
                                     int32_t skip, float p, uint64_t seed, int64_t n_rows, int32_t H, float* x_next,
                                     float* amax, const bgnn_csr_t* pool, int32_t reduce, float* partial,
                                     float* pooled, void* stream) {
-    BGNN_REQUIRE(H > 0 && H % 4 == 0, "sage_apply_pool: H must be a multiple of 4");
-    BGNN_REQUIRE(n_rows >= 0, "sage_apply_pool: negative n_rows");
-    BGNN_REQUIRE(n_rows == 0 || o, "sage_apply_pool: null o");
-    BGNN_REQUIRE(p >= 0.f && p < 1.f, "sage_apply_pool: dropout p must be in [0, 1)");
-    BGNN_REQUIRE((scale == nullptr) == (shift == nullptr), "sage_apply_pool: scale/shift must both be set or NULL");
-    BGNN_REQUIRE(!skip || x_prev, "sage_apply_pool: skip requires x_prev");
-    BGNN_REQUIRE(al16(o) && al16(x_next) && (!x_prev || al16(x_prev)) && (!scale || (al16(scale) && al16(shift))),
-                 "sage_apply_pool: pointers must be 16-byte aligned");
+    ApplyPoolArgs A{};
+    if (const int e =
+            apply_args(A, "sage_apply_pool", o, scale, shift, x_prev, skip, p, seed, n_rows, H, x_next, amax, false))
+        return e;
     BGNN_REQUIRE(pool && pool->rowptr, "sage_apply_pool: null pool csr");
     BGNN_REQUIRE(reduce == BGNN_REDUCE_SUM || reduce == BGNN_REDUCE_MEAN, "sage_apply_pool: reduce must be sum/mean");
     BGNN_REQUIRE(pool->n_rows >= 0, "sage_apply_pool: negative segment count");
@@ -1075,18 +849,9 @@ extern "C" int bgnn_sage_apply_pool(const float* o, const float* scale, const fl
     BGNN_REQUIRE(pool->n_chunks <= 0 ||
                      (partial && pool->chunk > 0 && pool->heavy_row && pool->heavy_chunk0 && pool->chunk_heavy),
                  "sage_apply_pool: heavy segments need partial and the CSR's chunk plan");
-    BGNN_REQUIRE(al16(partial) && al16(pooled), "sage_apply_pool: partial / pooled must be 16-byte aligned");
+    BGNN_REQUIRE(aligned16(partial) && aligned16(pooled), "sage_apply_pool: partial / pooled must be 16-byte aligned");
     if (n_rows == 0) return BGNN_OK;
     hipStream_t s = as_stream(stream);
-    ApplyPoolArgs A{};
-    A.o = o; A.scale = scale; A.shift = shift; A.xprev = x_prev;
-    A.thr = dropout_threshold(p);
-    A.inv_keep = A.thr ? 1.f / (1.f - p) : 1.f;
-    A.seed = seed;
-    A.H = H;
-    A.nt = rows_nt();
-    A.xn = x_next;
-    A.amax = reinterpret_cast<uint32_t*>(amax);
     A.rowptr = pool->rowptr; A.col = pool->col;
     A.heavy_row = pool->heavy_row; A.heavy_chunk0 = pool->heavy_chunk0; A.chunk_heavy = pool->chunk_heavy;
     A.n_chunks = pool->n_chunks > 0 ? pool->n_chunks : 0;
@@ -1101,8 +866,7 @@ extern "C" int bgnn_sage_apply_pool(const float* o, const float* scale, const fl
     A.ct = tiles <= 2 ? tiles : 4;   // (a divisor of the block's 4 waves; a tile past the row leaves at once)
     const int ipb = 4 / A.ct;        // items per block
     const dim3 grid((unsigned)((items + ipb - 1) / ipb), (unsigned)((tiles + A.ct - 1) / A.ct));
-    if (skip) hipLaunchKernelGGL(k_sage_apply_pool<true>, grid, dim3(256), 0, s, A);
-    else hipLaunchKernelGGL(k_sage_apply_pool<false>, grid, dim3(256), 0, s, A);
+    hipLaunchKernelGGL(skip ? k_sage_apply_pool<true> : k_sage_apply_pool<false>, grid, dim3(256), 0, s, A);
     BGNN_CHECK_LAUNCH();
     if (A.n_chunks > 0) return seg_combine_plain(pool, H, reduce, partial, pooled, s);
     return BGNN_OK;
@@ -1132,15 +896,15 @@ extern "C" int bgnn_sage_bwd_stats(const float* g, const int64_t* g_rows, const 
     BGNN_REQUIRE(H > 0 && H % 4 == 0 && H <= 1024, "sage_bwd_stats: H=%d unsupported", H);
     BGNN_REQUIRE(n_rows >= 0, "sage_bwd_stats: negative n_rows");
     BGNN_REQUIRE(g && o && scale && shift && mean && invstd && partial2, "sage_bwd_stats: null pointer");
-    BGNN_REQUIRE(al16(g) && al16(o) && al16(scale) && al16(shift) && al16(mean) && al16(invstd) && al16(partial2),
+    BGNN_REQUIRE(aligned16(g) && aligned16(o) && aligned16(scale) && aligned16(shift) && aligned16(mean) &&
+                     aligned16(invstd) && aligned16(partial2),
                  "sage_bwd_stats: pointers must be 16-byte aligned");
     hipStream_t s = as_stream(stream);
     int64_t rpb = 0;
     const int64_t blocks = rows_grid(n_rows, 4, &rpb);
-    const uint32_t thr = dropout_threshold(p);
-    const float inv_keep = thr ? 1.f / (1.f - p) : 1.f;
+    const Dropout d = dropout_of(p);
     hipLaunchKernelGGL(k_sage_bwd_stats, dim3((unsigned)blocks), dim3(256), 0, s, g, g_rows, o, scale, shift, mean, invstd,
-                       thr, inv_keep, seed, n_rows, H, rpb, partial2);
+                       d.thr, d.inv_keep, seed, n_rows, H, rpb, partial2);
     BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }
@@ -1160,30 +924,20 @@ extern "C" int bgnn_sage_bwd_rows(const float* g, const int64_t* g_rows, const f
     BGNN_REQUIRE(lddh >= H && lddh % 4 == 0, "sage_bwd_rows: bad lddh");
     BGNN_REQUIRE(!skip || gskip, "sage_bwd_rows: skip requires gskip");
     BGNN_REQUIRE(!mean || (invstd && sum_g2 && sum_g2xhat), "sage_bwd_rows: BN stats incomplete");
-    BGNN_REQUIRE(al16(g) && al16(o) && al16(dh) && (!gskip || al16(gskip)) && al16(partial_db),
+    BGNN_REQUIRE(aligned16(g) && aligned16(o) && aligned16(dh) && (!gskip || aligned16(gskip)) && aligned16(partial_db),
                  "sage_bwd_rows: pointers must be 16-byte aligned");
-    BGNN_REQUIRE(!ranges || (range_partial && al16(range_partial)), "sage_bwd_rows: ranges need range_partial");
-    hipStream_t s = as_stream(stream);
-    int64_t rpb = 0;
-    const int64_t blocks = rows_grid(n_rows, 4, &rpb);
-    const uint32_t thr = dropout_threshold(p);
-    const float inv_keep = thr ? 1.f / (1.f - p) : 1.f;
-#define BGNN_ROWS(NV, R)                                                                                              \
-    hipLaunchKernelGGL((k_sage_bwd_rows<NV, true, R>), dim3((unsigned)blocks), dim3(256), 0, s, g, g_rows, o, nrm,   \
-                       scale,                                                                                       \
-                       shift, gamma, mean, invstd, sum_g2, sum_g2xhat, thr, inv_keep, seed, skip, n_rows, H, rpb,    \
-                       dh, lddh, gskip, partial_db, reinterpret_cast<uint32_t*>(amax), rows_nt(), w_rowptr, w_mode,  \
-                       rows_rev() & 1, ranges, range_w_rowptr, range_partial)
-    if (ranges) {
-        if (H > 256) BGNN_ROWS(2, true);
-        else BGNN_ROWS(1, true);
-    } else {
-        if (H > 256) BGNN_ROWS(2, false);
-        else BGNN_ROWS(1, false);
-    }
-#undef BGNN_ROWS
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
+    BGNN_REQUIRE(!ranges || (range_partial && aligned16(range_partial)), "sage_bwd_rows: ranges need range_partial");
+    BwdRowsArgs A{};
+    A.g = g; A.g_rows = g_rows; A.o = o; A.nrm = nrm;
+    A.scale = scale; A.shift = shift; A.gamma = gamma; A.mean = mean; A.invstd = invstd;
+    A.sum_g2 = sum_g2; A.sum_g2xhat = sum_g2xhat;
+    A.drop = dropout_of(p); A.seed = seed; A.skip = skip;
+    A.n_rows = n_rows; A.H = H;
+    A.dh = dh; A.lddh = lddh; A.gskip = gskip;
+    A.part = partial_db; A.amax = amax;
+    A.w_rowptr = w_rowptr; A.w_mode = w_mode;
+    A.ranges = ranges; A.rw_rowptr = range_w_rowptr; A.rpart = range_partial;
+    return launch_bwd_rows(A, true, stream);
 }
 
 // The L2-normalize backward of SAGEConv(normalize=True) on its own (bgnn.nn.SAGEConv's fused
@@ -1196,20 +950,13 @@ extern "C" int bgnn_l2norm_bwd(const float* g, const float* o, const float* nrm,
     BGNN_REQUIRE(n_rows >= 0, "l2norm_bwd: negative n_rows");
     BGNN_REQUIRE(g && o && nrm && dh && partial_db && amax, "l2norm_bwd: null pointer");
     BGNN_REQUIRE(lddh >= H && lddh % 4 == 0, "l2norm_bwd: bad lddh");
-    BGNN_REQUIRE(al16(g) && al16(o) && al16(dh) && al16(partial_db), "l2norm_bwd: pointers must be 16-byte aligned");
-    hipStream_t s = as_stream(stream);
-    int64_t rpb = 0;
-    const int64_t blocks = rows_grid(n_rows, 4, &rpb);
-    if (H > 256)
-        hipLaunchKernelGGL((k_sage_bwd_rows<2, false>), dim3((unsigned)blocks), dim3(256), 0, s, g, nullptr, o, nrm, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 1.f, (uint64_t)0, 0, n_rows, H,
-                           rpb, dh, lddh, nullptr, partial_db, reinterpret_cast<uint32_t*>(amax), rows_nt(), nullptr,
-                           0, rows_rev() & 1, nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((k_sage_bwd_rows<1, false>), dim3((unsigned)blocks), dim3(256), 0, s, g, nullptr, o, nrm, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 1.f, (uint64_t)0, 0, n_rows, H,
-                           rpb, dh, lddh, nullptr, partial_db, reinterpret_cast<uint32_t*>(amax), rows_nt(), nullptr,
-                           0, rows_rev() & 1, nullptr, nullptr, nullptr);
-    BGNN_CHECK_LAUNCH();
-    return BGNN_OK;
+    BGNN_REQUIRE(aligned16(g) && aligned16(o) && aligned16(dh) && aligned16(partial_db),
+                 "l2norm_bwd: pointers must be 16-byte aligned");
+    BwdRowsArgs A{};
+    A.g = g; A.o = o; A.nrm = nrm;
+    A.drop.inv_keep = 1.f;
+    A.n_rows = n_rows; A.H = H;
+    A.dh = dh; A.lddh = lddh;
+    A.part = partial_db; A.amax = amax;
+    return launch_bwd_rows(A, false, stream);
 }
