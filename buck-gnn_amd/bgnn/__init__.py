@@ -20,7 +20,8 @@ from .train import ColumnScaler, EigenvalueScaler, GradAllReduce, RelativeErrorL
 from .fused import node_head
 from . import losses
 from .losses import (GraphMAELoss, GraphMaxComponentRelativeError, GraphMixedError, GraphMSELoss,
-                     GraphRelativeError, StressErrorMeter, graph_metrics, stress_errors)
+                     GraphRelativeError, ScaledGraphMAELoss, ScaledGraphMSELoss, ScaledGraphRELoss, StressErrorMeter,
+                     get_loss_function, graph_metrics, stress_errors)
 
 __all__ = [
     "BuckGNN", "GraphNetBlock", "MLPPooling", "Batch", "Data", "DataLoader", "Graph", "SegmentIndex",
@@ -30,7 +31,8 @@ __all__ = [
     "mape_error", "train_step", "load_library", "GraphStore", "load_checkpoint", "load_reference_checkpoint",
     "save_checkpoint", "load_dataset_cache", "evaluate", "losses", "GraphMAELoss", "GraphMaxComponentRelativeError", "GraphMixedError",
     "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head",
-    "evaluate_nodes", "StressErrorMeter", "graph_metrics",
+    "evaluate_nodes", "StressErrorMeter", "graph_metrics", "ScaledGraphMAELoss", "ScaledGraphMSELoss",
+    "ScaledGraphRELoss", "get_loss_function",
 ]
 
 

@@ -175,6 +175,11 @@ SIGNATURES = {
     "bgnn_graph_metrics_ws_bytes": (c_sz, [c_i64, c_i32, c_i64]),
     "bgnn_graph_metrics": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_i32, c_f32, c_p, c_p, c_p, c_p, c_sz,
                                    c_p]),
+    "bgnn_graph_loss_ex_ws_bytes": (c_sz, [c_i64, c_i32, c_i64]),
+    "bgnn_graph_loss_ex": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_i32, c_f32, c_f32, c_p, c_p, c_f32,
+                                   c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "bgnn_force_scale_ws_bytes": (c_sz, [c_i64]),
+    "bgnn_force_scale": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_f32, c_p, c_p, c_sz, c_p]),
     "bgnn_gemm_f32_dropadd": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p,
                                       c_p, c_p, c_i64, c_f32, c_u64, c_p, c_sz, c_p]),
     "bgnn_gemm_f32_dropadd_cols": (c_i32, [c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p,

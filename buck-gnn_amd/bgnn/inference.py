@@ -18,7 +18,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from .graph import prepare
-from .train import ColumnScaler, EigenvalueScaler, _denormalize_nodes
+from .train import ColumnScaler, EigenvalueScaler, _denormalize_nodes, _node_criterion
 
 
 @torch.no_grad()
@@ -72,7 +72,9 @@ def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, th
     TRAIN_FINAL.py:349-384): eval mode, no_grad, per batch the model's prediction and its returned
     (super-node adjusted) batch vector, stress_errors of the denormalised values accumulated in a
     StressErrorMeter (threshold None: the reference's, 1e-4 for static_disp and 0.2 for
-    static_stress), and criterion(denorm(pred), denorm(y), batch, None) when a criterion is given.
+    static_stress), and criterion(denorm(pred), denorm(y), batch, x) as the train step calls it (x: the
+    node features without the super nodes, for a criterion that reads the forces) when a criterion is
+    given.
     normalizer: a bgnn.ColumnScaler (folded into the metric kernel), a reference-style object with
     denormalize_displacement / denormalize_gp_stresses, or None.
     Returns {"metrics_per_graph": sums / graphs, "metrics_per_batch": sums / batches, "graphs",
@@ -98,8 +100,7 @@ def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, th
             meter.update(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
                          out_batch)
         if criterion is not None:
-            v = criterion(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
-                          out_batch, None).detach().double()
+            v = _node_criterion(model, batch, criterion, normalizer, pred, y, out_batch).detach().double()
             loss_sum = v if loss_sum is None else loss_sum + v
     graphs, n = meter.counts
     return {"metrics_per_graph": meter.compute("graph"), "metrics_per_batch": meter.compute("batch"), "graphs": graphs,

@@ -17,7 +17,20 @@ Semantics kept from the reference, including its quirks:
 * `GraphMixedError` uses the 0.2-quantile of the relative error (its docstring says P90);
 * `stress_errors` returns SUMS over graphs (its comment says means), and the `*_high` /
   `*_low` entries sum only over graphs that have such elements (0 when none has);
-* per-component maxima take the first index of the largest |target| (torch.argmax).
+* per-component maxima take the first index of the largest |target| (torch.argmax);
+* the force-scaled losses (`ScaledGraphMAELoss`, `ScaledGraphMSELoss`, `ScaledGraphRELoss`) scale by
+  100, not 10000, sum the force over every row of the `x` they are given (one scale for the whole
+  batch, not one per graph), and `ScaledGraphMSELoss` without a batch vector returns mean |p - t| times
+  the scale (no squares).
+
+All eight `criterion(pred, target, batch, x)` classes of the reference run on HIP when they are given
+a batch vector and float32 GPU tensors of at most 8 columns (`graph_loss`, `criterion_loss`):
+bgnn_graph_loss for the three per-graph means, bgnn_graph_loss_ex for the mixed (exact per-graph
+quantile by radix select, with its gradient), max-component and force-scaled ones, the force scale
+itself from bgnn_force_scale on the device (no `.item()`). Loss and gradient come from one call, sums
+in double in a fixed order, bit-stable. `FUSED_GRAPH_LOSS = False`, a name taken out of
+`FUSED_CRITERIA`, CPU tensors, doubles and more than 8 columns run the torch segment ops.
+`get_loss_function` maps the reference's loss names to these classes.
 
 `stress_errors` on float32 GPU tensors runs as one HIP entry point (`graph_metrics`,
 bgnn_graph_metrics: the whole per-graph table of `METRIC_KEYS[prediction_type]` in two launches,
@@ -123,20 +136,65 @@ class _GraphLossFn(torch.autograd.Function):
         return dpred * g, None, None, None, None, None, None
 
 
-def _segments(batch: Tensor):
+def _segments(batch: Tensor, num_graphs: Optional[int] = None):
+    """The batch vector's segment index (cached); num_graphs: the graph count where the caller
+    knows it (None: read back from the batch vector)."""
     from .graph import SegmentIndex, _index_cache
 
     def build():
-        return SegmentIndex.build(batch, int(batch.max().item()) + 1)
+        return SegmentIndex.build(batch, int(batch.max().item()) + 1 if num_graphs is None else int(num_graphs))
     return _index_cache.get(batch, ("batch",), build)
 
 
+class _GraphLossExFn(torch.autograd.Function):
+    """bgnn_graph_loss_ex: kinds 0..5 with the quantile q and the multiplier mult * mult_dev[0]
+    (mult_dev: a float32 device scalar or None; no gradient flows through it), otherwise as
+    _GraphLossFn."""
+
+    @staticmethod
+    def forward(ctx, pred, target, seg, kind: int, eps: float, scale, center, q: float, mult: float, mult_dev):
+        from . import _lib
+        from .graph import _ptr, _stream
+        shape = pred.shape
+        p = pred.contiguous()
+        t = target.contiguous()
+        N = p.size(0)
+        C = p.numel() // N
+        B = seg.num_rows
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        dpred = torch.empty_like(p)
+        ws_bytes = _lib.query("bgnn_graph_loss_ex_ws_bytes", N, C, B)
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=p.device)
+        _lib.call("bgnn_graph_loss_ex", p.data_ptr(), t.data_ptr(), N, C, seg.fwd.rowptr.data_ptr(),
+                  seg.fwd.col.data_ptr(), B, int(kind), float(eps), float(mult), _ptr(scale), _ptr(center), float(q),
+                  _ptr(mult_dev), loss.data_ptr(), dpred.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+        ctx.save_for_backward(dpred.view(shape))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dpred,) = ctx.saved_tensors
+        return (dpred * g,) + (None,) * 9
+
+
+# the reference's factor per kind: the per-graph means and the max-component loss x 10000, the
+# force-scaled ratio of sums x 100, the mixed loss as it is
+_KIND_MULT = {0: _MULT, 1: _MULT, 2: _MULT, 3: 100.0, 4: 1.0, 5: _MULT}
+
+
 def graph_loss(kind: int, eps: float, pred: Tensor, target: Tensor, batch: Optional[Tensor], scale=None,
-               center=None) -> Optional[Tensor]:
-    """The per-graph-mean loss `kind` (0 relative, 1 MAE, 2 squares) of pred * scale + center against
-    target * scale + center (scale / center: [C] float32 tensors or None) on bgnn_graph_loss, or
-    None when the call does not qualify: float32 GPU pred and target of one [N] or [N, C <= 8] shape,
-    a batch vector of N graph ids on the same device, no gradient wanted for target."""
+               center=None, q: float = 0.0, mult: Optional[float] = None, mult_dev: Optional[Tensor] = None,
+               num_graphs: Optional[int] = None) -> Optional[Tensor]:
+    """The per-graph loss `kind` (0 relative, 1 MAE, 2 squares: per-graph means; 3 ratio of sums, 4
+    mixed with the `q`-quantile of the relative error, 5 relative error at each component's largest
+    |target|) of pred * scale + center against target * scale + center (scale / center: [C] float32
+    tensors or None), times mult (None: the reference's factor for the kind, 10000 / 100 / 1) and
+    times mult_dev[0] (a float32 device scalar, e.g. force_scale's; None: 1), or None when the call
+    does not qualify: float32 GPU pred and target of one [N] or [N, C <= 8] shape, a batch vector of
+    N graph ids on the same device, no gradient wanted for target. num_graphs: the number of graphs
+    where the caller knows it (it saves the read-back of batch.max()). Kinds 0..2 with the default
+    multiplier run on bgnn_graph_loss, everything else on bgnn_graph_loss_ex (fewer than 2^31
+    elements)."""
     if not (FUSED_GRAPH_LOSS and batch is not None and pred.is_cuda and pred.dtype == torch.float32
             and target.dtype == torch.float32 and target.device == pred.device and pred.shape == target.shape
             and pred.dim() in (1, 2) and pred.size(0) > 0 and batch.device == pred.device and batch.dim() == 1
@@ -148,7 +206,37 @@ def graph_loss(kind: int, eps: float, pred: Tensor, target: Tensor, batch: Optio
     for v in (scale, center):
         if v is not None and not (v.is_cuda and v.dtype == torch.float32 and v.numel() == C and v.is_contiguous()):
             return None
-    return _GraphLossFn.apply(pred, target, _segments(batch), kind, eps, scale, center)
+    if kind <= 2 and mult is None and mult_dev is None:
+        return _GraphLossFn.apply(pred, target, _segments(batch, num_graphs), kind, eps, scale, center)
+    if kind not in _KIND_MULT or pred.numel() >= 2 ** 31 or (kind == 4 and not 0.0 <= q <= 1.0):
+        return None
+    if mult_dev is not None and not (mult_dev.is_cuda and mult_dev.device == pred.device
+                                     and mult_dev.dtype == torch.float32 and mult_dev.numel() == 1):
+        return None
+    return _GraphLossExFn.apply(pred, target, _segments(batch, num_graphs), kind, eps, scale, center, q,
+                                _KIND_MULT[kind] if mult is None else mult, mult_dev)
+
+
+def force_scale(x: Tensor, min_scale: float, flag_col: Optional[int] = None, c0: int = 3, nc: int = 2
+                ) -> Optional[Tensor]:
+    """max(sum over rows of ||x[:, c0 : c0 + nc]||_2, min_scale) as a float32 device scalar [1] on
+    bgnn_force_scale (the Scaled* classes' compute_total_force and clamp, no host read); rows with a
+    non-zero x[:, flag_col] are skipped (None: every row counts). None when the call does not
+    qualify: a float32 GPU x [N >= 1, F >= c0 + nc] with unit column stride."""
+    if not (FUSED_GRAPH_LOSS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) > 0
+            and x.stride(1) == 1 and x.stride(0) >= x.size(1) and 1 <= nc <= 8 and 0 <= c0
+            and c0 + nc <= x.size(1) and (flag_col is None or 0 <= flag_col < x.size(1))):
+        return None
+    from . import _lib
+    from .graph import _stream
+    x = x.detach()
+    N = x.size(0)
+    out = torch.empty(1, dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.query("bgnn_force_scale_ws_bytes", N)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=x.device)
+    _lib.call("bgnn_force_scale", x.data_ptr(), N, x.stride(0), c0, nc, -1 if flag_col is None else int(flag_col),
+              float(min_scale), out.data_ptr(), ws.data_ptr(), ws_bytes, _stream())
+    return out
 
 
 # --------------------------------------------------------------------------------------------
@@ -183,6 +271,9 @@ class GraphMixedError(nn.Module):
         self.percentile = percentile
 
     def forward(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], x=None) -> Tensor:
+        out = criterion_loss(self, pred, target, batch)
+        if out is not None:
+            return out
         diff = torch.abs(pred - target)
         rel = diff / (torch.abs(target) + self.epsilon)
         if batch is None:
@@ -238,6 +329,9 @@ class GraphMaxComponentRelativeError(nn.Module):
         self.epsilon = epsilon
 
     def forward(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], x=None) -> Tensor:
+        out = criterion_loss(self, pred, target, batch)
+        if out is not None:
+            return out
         p2 = pred if pred.dim() > 1 else pred.unsqueeze(1)
         t2 = target if target.dim() > 1 else target.unsqueeze(1)
         if batch is None:
@@ -251,6 +345,157 @@ class GraphMaxComponentRelativeError(nn.Module):
             mt, mp = t2[i, c], p2[i, c]
             errs.append(torch.abs(mp - mt) / (torch.abs(mt) + self.epsilon))
         return torch.mean(torch.stack(errs, 1)) * 10000
+
+
+class _ScaledGraphLoss(nn.Module):
+    """The force-scaled per-graph losses (Utils/Losses.py:509-695): the per-graph term times
+    max(total force, min_scale), averaged over graphs, x 100. The total force is the sum over ALL
+    rows of the x passed in of ||x[:, 3:5]||_2, not per graph: one scale serves every graph of the
+    batch, and no gradient flows through it. Without a batch vector: the term over all elements times
+    the scale, not x 100."""
+
+    _kind = 1   # the kernel's kind (graph_loss) of the per-graph term
+
+    def __init__(self, force_scaling: bool = True, min_scale: float = 0.1):
+        super().__init__()
+        self.force_scaling = force_scaling
+        self.min_scale = min_scale
+
+    def compute_total_force(self, x: Tensor) -> Tensor:
+        return torch.sum(torch.norm(x[:, 3:5], dim=1))
+
+    def _scale(self, x: Optional[Tensor]):
+        """max(total force, min_scale) as a tensor (the reference reads it back with .item()), or 1."""
+        if not self.force_scaling:
+            return 1.0
+        if x is None:
+            raise ValueError(f"{type(self).__name__}: force_scaling needs the node features x "
+                             "(forces in columns 3:5); pass x or construct with force_scaling=False")
+        return torch.clamp(self.compute_total_force(x.detach()), min=self.min_scale)
+
+    def _term(self, pred: Tensor, target: Tensor) -> Tensor:
+        return torch.abs(pred - target)
+
+    def _all(self, pred: Tensor, target: Tensor) -> Tensor:
+        """The term without a batch vector."""
+        return torch.mean(torch.abs(pred - target))
+
+    def _per_graph(self, pred: Tensor, target: Tensor, batch: Tensor, n: int) -> Tensor:
+        d = self._term(pred, target)
+        return _seg_mean(d.reshape(-1), _elem_seg(batch, d), n)
+
+    def forward(self, pred: Tensor, target: Tensor, batch: Optional[Tensor], x: Optional[Tensor] = None) -> Tensor:
+        out = criterion_loss(self, pred, target, batch, x)
+        if out is not None:
+            return out
+        scale = self._scale(x)
+        if batch is None:
+            return self._all(pred, target) * scale
+        return torch.mean(self._per_graph(pred, target, batch, _num_graphs(batch)) * scale) * 100
+
+
+class ScaledGraphMAELoss(_ScaledGraphLoss):
+    """Per-graph mean of |p - t| times the force scale, averaged over graphs, x 100
+    (Utils/Losses.py:509-566)."""
+
+
+class ScaledGraphMSELoss(_ScaledGraphLoss):
+    """Per-graph mean of |p^2 - t^2| times the force scale, averaged over graphs, x 100; without a
+    batch vector mean |p - t| times the scale (Utils/Losses.py:568-625)."""
+
+    _kind = 2
+
+    def _term(self, pred: Tensor, target: Tensor) -> Tensor:
+        return torch.abs(pred ** 2 - target ** 2)
+
+
+class ScaledGraphRELoss(_ScaledGraphLoss):
+    """Per graph sum |p - t| / (sum |t| + 1e-8) times the force scale, averaged over graphs, x 100
+    (Utils/Losses.py:627-695)."""
+
+    _kind = 3
+
+    def _all(self, pred: Tensor, target: Tensor) -> Tensor:
+        return torch.abs(pred - target).sum() / (torch.abs(target).sum() + 1e-8)
+
+    def _per_graph(self, pred: Tensor, target: Tensor, batch: Tensor, n: int) -> Tensor:
+        seg = _elem_seg(batch, pred)
+        return _seg_sum(torch.abs(pred - target).reshape(-1), seg, n) / (
+            _seg_sum(torch.abs(target).reshape(-1), seg, n) + 1e-8)
+
+
+# The reference's names (get_loss_function) of the classes whose batch-vector call takes the
+# kernels of bgnn_graph_loss_ex while FUSED_GRAPH_LOSS is on. A name stays here only where
+# tools/graph_loss_ab.py measured its fused train step faster than the torch route (DESIGN §3k).
+FUSED_CRITERIA = {"graph_mixed", "graph_max_rel", "graph_mae_scaled", "graph_mse_scaled", "graph_rel_scaled"}
+
+
+def criterion_loss(criterion, pred: Tensor, target: Tensor, batch: Optional[Tensor], x: Optional[Tensor] = None,
+                   scale=None, center=None, flag_col: Optional[int] = None, num_graphs: Optional[int] = None
+                   ) -> Optional[Tensor]:
+    """criterion(pred * scale + center, target * scale + center, batch, x) for one of this module's
+    eight per-graph classes on the loss kernels (graph_loss), or None when the criterion is none of
+    them, is switched off (FUSED_GRAPH_LOSS, FUSED_CRITERIA) or the call does not qualify. For the
+    force-scaled classes x is the unfiltered node features and flag_col the column whose non-zero
+    rows (super nodes) do not count: the scale comes from force_scale, with no host read. num_graphs:
+    as graph_loss's."""
+    cls = type(criterion)
+    if batch is None:
+        return None
+    if cls in (GraphRelativeError, GraphMAELoss, GraphMSELoss):
+        kind = {GraphRelativeError: 0, GraphMAELoss: 1, GraphMSELoss: 2}[cls]
+        return graph_loss(kind, getattr(criterion, "epsilon", 0.0), pred, target, batch, scale, center,
+                          num_graphs=num_graphs)
+    name = _CRITERION_NAMES.get(cls)
+    if name is None or name not in FUSED_CRITERIA:
+        return None
+    if cls is GraphMixedError:
+        return graph_loss(4, criterion.epsilon, pred, target, batch, scale, center, q=criterion.percentile,
+                          num_graphs=num_graphs)
+    if cls is GraphMaxComponentRelativeError:
+        return graph_loss(5, criterion.epsilon, pred, target, batch, scale, center, mult=_MULT,
+                          num_graphs=num_graphs)
+    mult_dev = None
+    if criterion.force_scaling:
+        if x is None:
+            criterion._scale(None)   # raises
+        mult_dev = force_scale(x, criterion.min_scale, flag_col)
+        if mult_dev is None:
+            return None
+    return graph_loss(criterion._kind, 0.0, pred, target, batch, scale, center, mult=100.0, mult_dev=mult_dev,
+                      num_graphs=num_graphs)
+
+
+_CRITERION_NAMES = {GraphMixedError: "graph_mixed", GraphMaxComponentRelativeError: "graph_max_rel",
+                    ScaledGraphMAELoss: "graph_mae_scaled", ScaledGraphMSELoss: "graph_mse_scaled",
+                    ScaledGraphRELoss: "graph_rel_scaled"}
+# the classes whose forward takes (pred, target, batch, x)
+GRAPH_CRITERIA = (GraphRelativeError, GraphMAELoss, GraphMSELoss, GraphMixedError, GraphMaxComponentRelativeError,
+                  ScaledGraphMAELoss, ScaledGraphMSELoss, ScaledGraphRELoss)
+
+# get_loss_function's names that the reference maps to two-argument losses this package does not carry
+_REFERENCE_ONLY = ("static_mixed", "static_mse", "static_relative", "static_stress", "static_mae", "log_cosh",
+                   "eigenvalue", "order_preserving", "focal", "mape", "mae", "rse", "rrse", "rrse1", "msle",
+                   "focal_rrse", "focal_mape")
+
+
+def get_loss_function(loss_name: str, allValues=None, use_z_coord: bool = False, use_rotations: bool = False):
+    """The reference's get_loss_function (Utils/Losses.py:8-66) for the losses this package carries:
+    the eight graph_* names (criterion(pred, target, batch, x)), relative_error and mse. The
+    reference's other names raise NotImplementedError, an unknown name its ValueError."""
+    table = {"graph_mse": GraphMSELoss, "graph_mae": GraphMAELoss, "graph_rel": GraphRelativeError,
+             "graph_mixed": GraphMixedError, "graph_max_rel": GraphMaxComponentRelativeError,
+             "graph_rel_scaled": ScaledGraphRELoss, "graph_mae_scaled": ScaledGraphMAELoss,
+             "graph_mse_scaled": ScaledGraphMSELoss, "mse": nn.MSELoss}
+    if loss_name in table:
+        return table[loss_name]()
+    if loss_name == "relative_error":
+        from .train import RelativeErrorLoss
+        return RelativeErrorLoss()
+    if loss_name in _REFERENCE_ONLY:
+        raise NotImplementedError(f"get_loss_function: the reference's {loss_name!r} loss is not implemented in bgnn "
+                                  "(the graph_* losses, relative_error and mse are)")
+    raise ValueError(f"Unknown loss function: {loss_name}")
 
 
 # --------------------------------------------------------------------------------------------

@@ -150,33 +150,44 @@ def _denormalize_nodes(normalizer, prediction_type: str, v):
     return v
 
 
+def _node_criterion(model, batch, criterion, normalizer, pred, y, out_batch, num_graphs=None):
+    """criterion(denorm(pred), denorm(y), out_batch, x) of the node-level heads (TRAIN_FINAL.py:255-297).
+    With one of bgnn.losses' eight per-graph classes and a ColumnScaler (or no normalizer) the
+    denormalisation runs inside the loss kernel (losses.criterion_loss); the force-scaled classes
+    then take batch.x as it is, with the super-node flag column named instead of filtered on.
+    Otherwise x is the reference's: the rows of batch.x that are no super nodes."""
+    from . import losses
+    ptype = model.prediction_type
+    sup = "super" in model.pooling_layer
+    if isinstance(criterion, losses.GRAPH_CRITERIA) and (normalizer is None or type(normalizer) is ColumnScaler):
+        scale, center = normalizer._at(pred.device) if normalizer is not None else (None, None)
+        loss = losses.criterion_loss(criterion, pred, y, out_batch, batch.x, scale, center,
+                                     flag_col=batch.x.size(1) - 1 if sup else None, num_graphs=num_graphs)
+        if loss is not None:
+            return loss
+    if isinstance(criterion, (losses.GraphRelativeError, losses.GraphMAELoss, losses.GraphMSELoss,
+                              losses.GraphMixedError, losses.GraphMaxComponentRelativeError)):
+        fx = None   # (these classes ignore x: no gather)
+    elif sup:
+        fx = batch.x[batch.x[:, -1] == 0]
+    else:
+        fx = batch.x
+    return criterion(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
+                     out_batch, fx)
+
+
 def _train_step_nodes(model, batch, optimizer, criterion, normalizer, allreduce, sync_metrics: bool, metrics=None):
     """train_step for the node-level heads (prediction_type static_disp / static_stress /
-    mode_shape; TRAIN_FINAL.py:255-297): criterion(denorm(pred), denorm(y), adjusted batch, x).
-    With one of bgnn.losses' three per-graph-mean classes and a ColumnScaler (or no normalizer) the
-    denormalisation runs inside the loss kernel (losses.graph_loss). metrics: a
-    losses.StressErrorMeter that takes the step's detached prediction and the targets
-    (TRAIN_FINAL.py:271-292: stress_errors on the denormalised values, every step)."""
+    mode_shape; TRAIN_FINAL.py:255-297): criterion(denorm(pred), denorm(y), adjusted batch, x)
+    (_node_criterion). metrics: a losses.StressErrorMeter that takes the step's detached prediction and
+    the targets (TRAIN_FINAL.py:271-292: stress_errors on the denormalised values, every step)."""
     from . import losses
-    prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
+    _, seg = prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
     pred, out_batch = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)
     ptype = model.prediction_type
     y = batch.y.contiguous() if ptype == "static_stress" else batch.y
-    kind = {losses.GraphRelativeError: 0, losses.GraphMAELoss: 1, losses.GraphMSELoss: 2}.get(type(criterion))
-    loss = None
-    if kind is not None and (normalizer is None or type(normalizer) is ColumnScaler):
-        scale, center = normalizer._at(pred.device) if normalizer is not None else (None, None)
-        loss = losses.graph_loss(kind, getattr(criterion, "epsilon", 0.0), pred, y, out_batch, scale, center)
-    if loss is None:
-        if isinstance(criterion, (losses.GraphRelativeError, losses.GraphMAELoss, losses.GraphMSELoss,
-                                  losses.GraphMixedError, losses.GraphMaxComponentRelativeError)):
-            fx = None   # (the bgnn classes ignore x: no gather)
-        elif "super" in model.pooling_layer:
-            fx = batch.x[batch.x[:, -1] == 0]
-        else:
-            fx = batch.x
-        loss = criterion(_denormalize_nodes(normalizer, ptype, pred), _denormalize_nodes(normalizer, ptype, y),
-                         out_batch, fx)
+    loss = _node_criterion(model, batch, criterion, normalizer, pred, y, out_batch,
+                           seg.num_rows if seg is not None else None)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     if allreduce is not None:

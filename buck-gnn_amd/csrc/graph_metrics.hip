@@ -12,35 +12,18 @@
 // +inf): four 8-bit passes with a 256-bin integer histogram in LDS give the value of rank lo; rank
 // lo + 1 is the same value when the bin holds more of it, else the smallest larger element (one
 // more pass, an integer minimum). The elements are recomputed from pred / target in every pass
-// (L2-resident); nothing is staged, so a graph's size has no upper limit.
+// (L2-resident); nothing is staged, so a graph's size has no upper limit. The select, the block
+// reductions and the element terms live in graph_select.h, shared with graph_loss_ex.hip.
 //
 // Arithmetic: every element term in f32 with torch's roundings (each product, sum, difference and
 // quotient rounded, no contraction); every sum in double, per thread in walk order, then lanes and
 // waves by a fixed butterfly; no floating-point atomics (the histogram and the minimum are integer
 // LDS atomics, which are order-independent). The table is bit-identical from run to run.
-#include "common.h"
-
-#include <limits.h>
+#include "graph_select.h"
 
 namespace bgnn {
 
 namespace {
-
-constexpr int kMT = 256;                       // threads per workgroup (sums)
-constexpr int kQT = 1024;                      // threads per workgroup (selects: 41 VGPRs, walks are latency-bound)
-constexpr int kMW = kMT / kWave;               // waves per workgroup
-constexpr uint32_t kNanBits = 0x7FC00000u;     // every NaN sorts as this pattern (above +inf)
-
-// ---- block reductions, fixed order, result on every thread. `sh` is scratch of kMW entries.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    for (int m = kWave >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, kWave);
-    __syncthreads();   // (the scratch of the call before is read by now)
-    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = v;
-    __syncthreads();
-    double s = sh[0];
-    for (int w = 1; w < kMW; ++w) s += sh[w];
-    return s;
-}
 
 __device__ __forceinline__ long long block_sum_i(long long v, long long* sh) {
     for (int m = kWave >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, kWave);
@@ -63,59 +46,6 @@ __device__ __forceinline__ float block_nan_max(float v, float* sh) {
     float s = sh[0];
     for (int w = 1; w < kMW; ++w) s = nan_max(s, sh[w]);
     return s;
-}
-
-// (value, row) of the largest value; ties to the smallest row. Values are finite and >= 0.
-__device__ __forceinline__ void arg_better(float& v, int& r, float v2, int r2) {
-    if (v2 > v || (v2 == v && r2 < r)) {
-        v = v2;
-        r = r2;
-    }
-}
-
-__device__ __forceinline__ int block_argmax(float v, int r, float* shv, int* shr) {
-    for (int m = kWave >> 1; m > 0; m >>= 1) {
-        const float v2 = __shfl_xor(v, m, kWave);
-        const int r2 = __shfl_xor(r, m, kWave);
-        arg_better(v, r, v2, r2);
-    }
-    __syncthreads();
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        shv[threadIdx.x / kWave] = v;
-        shr[threadIdx.x / kWave] = r;
-    }
-    __syncthreads();
-    float bv = shv[0];
-    int br = shr[0];
-    for (int w = 1; w < kMW; ++w) arg_better(bv, br, shv[w], shr[w]);
-    return br;
-}
-
-// ---- the element terms, f32 with torch's roundings
-struct Denorm {
-    const float* scale;
-    const float* center;
-    __device__ __forceinline__ float operator()(float v, int c) const {
-        if (scale) v = __fmul_rn(v, scale[c]);
-        if (center) v = __fadd_rn(v, center[c]);
-        return v;
-    }
-};
-
-__device__ __forceinline__ float abs_diff_of(float t, float p) { return fabsf(__fsub_rn(t, p)); }
-__device__ __forceinline__ float rel_diff_of(float a, float t) { return __fdiv_rn(a, __fadd_rn(fabsf(t), 1e-8f)); }
-
-// sqrt(sum_c v_c^2): squares and sums rounded one by one in column order, the root correctly rounded
-// (v(c): the row's value in column c; no per-thread arrays, a runtime C would put them in scratch)
-template <class F>
-__device__ __forceinline__ float row_norm(F&& v, int C) {
-    const float v0 = v(0);
-    float acc = __fmul_rn(v0, v0);
-    for (int c = 1; c < C; ++c) {
-        const float vc = v(c);
-        acc = __fadd_rn(acc, __fmul_rn(vc, vc));
-    }
-    return sqrtf(acc);   // correctly rounded (hipcc's default; __fsqrt_rn is the 1-ulp native root here)
 }
 
 struct RegionSums {
@@ -259,12 +189,6 @@ __global__ __launch_bounds__(kMT) void k_graph_metrics_sums(const float* __restr
     o[kColNLow] = (double)lo.n;
 }
 
-// torch.quantile's linear interpolation, restated in f32 with explicit roundings
-__device__ __forceinline__ float lerp_f32(float a, float b, float w) {
-    const float d = __fsub_rn(b, a);
-    return w < 0.5f ? __fadd_rn(a, __fmul_rn(w, d)) : __fsub_rn(b, __fmul_rn(d, __fsub_rn(1.f, w)));
-}
-
 // block (g, which): which 0 / 1 / 2: the relative error over the high region / the low region / all
 // elements, 3: the absolute error over all elements. Element counts come from the sums kernel's
 // count columns. Writes (x 100 for the relative ones) into the p90 columns.
@@ -274,9 +198,7 @@ __global__ __launch_bounds__(kQT) void k_graph_quantiles(const float* __restrict
                                                          const int32_t* __restrict__ col, int mode, float threshold,
                                                          float q, const float* __restrict__ scale,
                                                          const float* __restrict__ center, double* __restrict__ out) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t scan[256];
-    __shared__ uint32_t s_prefix, s_k, s_eq, s_min, s_nan;
+    __shared__ SelectShared sh;
     const int t = threadIdx.x;
     const int g = blockIdx.x, which = blockIdx.y;
     const int64_t r0 = rowptr[g], r1 = rowptr[g + 1];
@@ -288,12 +210,7 @@ __global__ __launch_bounds__(kQT) void k_graph_quantiles(const float* __restrict
         if (t == 0) o[ocol] = 0.0;
         return;
     }
-    // torch.quantile: rank = q * (n - 1) in f32, the two neighbours, weight = rank - floor
-    const float rank = __fmul_rn(q, (float)(n - 1));
-    const float below = floorf(rank);
-    const int64_t k_lo = (int64_t)below;
-    const bool need_hi = (int64_t)ceilf(rank) > k_lo;
-    const float w = __fsub_rn(rank, below);
+    const QuantileRank rk = quantile_rank(q, n);   // (k_lo < n <= N C < 2^31: the entry's check)
     const Denorm dn{scale, center};
 
     // Walks the graph's elements of this block's set: f(bits) for each. Every pass recomputes them.
@@ -312,61 +229,17 @@ __global__ __launch_bounds__(kQT) void k_graph_quantiles(const float* __restrict
                 }
                 const float a = abs_diff_of(tv, dn(pp[c], c));
                 const float v = which == 3 ? a : rel_diff_of(a, tv);
-                f(v != v ? kNanBits : __float_as_uint(v));
+                f(select_bits(v));
             }
         }
     };
 
-    if (t == 0) {
-        s_prefix = 0;
-        s_k = (uint32_t)k_lo;   // (k_lo < n <= N C < 2^31: the entry's check)
-        s_nan = 0;
-        s_min = 0xFFFFFFFFu;
-    }
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (t < 256) hist[t] = 0;
-        __syncthreads();
-        const uint32_t prefix = s_prefix;
-        const uint32_t mask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
-        walk([&](uint32_t b) {
-            if (shift == 24 && b == kNanBits) s_nan = 1;   // (same value from every writer)
-            if ((b & mask) == prefix) atomicAdd(&hist[(b >> shift) & 255u], 1u);
-        });
-        __syncthreads();
-        // inclusive scan of the 256 bins by the first 256 threads (Hillis-Steele, two buffers folded
-        // into one with barriers; every thread takes the barriers)
-        const bool bin = t < 256;
-        const uint32_t v = bin ? hist[t] : 0u;
-        if (bin) scan[t] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const uint32_t add = (bin && t >= d) ? scan[t - d] : 0u;
-            __syncthreads();
-            if (bin) scan[t] += add;
-            __syncthreads();
-        }
-        const uint32_t incl = bin ? scan[t] : 0u, excl = incl - v, k = s_k;
-        __syncthreads();
-        if (bin && k >= excl && k < incl) {   // exactly one bin holds rank k
-            s_prefix = prefix | ((uint32_t)t << shift);
-            s_k = k - excl;
-            s_eq = v;
-        }
-        __syncthreads();
-    }
-    const uint32_t lo_bits = s_prefix;
-    uint32_t hi_bits = lo_bits;
-    if (need_hi && s_k + 1 >= s_eq) {   // rank lo + 1 lies past the copies of the value: the next larger one
-        walk([&](uint32_t b) {
-            if (b > lo_bits) atomicMin(&s_min, b);
-        });
-        __syncthreads();
-        hi_bits = s_min;
-    }
+    const Selected sel = radix_select(sh, walk, (uint32_t)rk.k_lo, rk.need_hi);
     if (t == 0) {
         float res;
-        if (s_nan) res = __uint_as_float(kNanBits);   // torch.quantile: any NaN in the set gives NaN
-        else res = need_hi ? lerp_f32(__uint_as_float(lo_bits), __uint_as_float(hi_bits), w) : __uint_as_float(lo_bits);
+        if (sel.has_nan) res = __uint_as_float(kNanBits);   // torch.quantile: any NaN in the set gives NaN
+        else res = rk.need_hi ? lerp_f32(__uint_as_float(sel.lo_bits), __uint_as_float(sel.hi_bits), rk.w)
+                              : __uint_as_float(sel.lo_bits);
         o[ocol] = which == 3 ? (double)res : (double)res * 100.0;
     }
 }

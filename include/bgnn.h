@@ -1021,6 +1021,65 @@ int bgnn_graph_metrics(const float* pred, const float* target, int64_t N, int32_
                        const int32_t* col, int64_t B, int32_t mode, float threshold, const float* scale,
                        const float* center, void* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The rest of the reference's criterion(pred, target, batch, x) family (Utils/Losses.py:303-359,
+ * 403-443, 509-695); additive to ABI 22 (new symbols only). bgnn_graph_loss_ex takes
+ * bgnn_graph_loss's arguments and conventions (pred / target [N, C] row-major, 1 <= C <= 8, the batch
+ * vector's segment CSR in any row order, p' = pred * scale[c] + center[c] and t' likewise with
+ * torch's f32 roundings, sums in double by fixed trees, sign(0) = sign(NaN) = 0, no floating-point
+ * atomics: loss and gradient bit-identical from run to run), plus q (the quantile of kind 4, in
+ * [0, 1]) and mult_dev, an optional device scalar: the effective multiplier is m = mult * *mult_dev
+ * (NULL: m = mult), read by the kernels, so a device-computed scale costs no host read. N C < 2^31.
+ * dpred = d loss / d pred (NULL: skipped).
+ *   kinds 0, 1, 2: as bgnn_graph_loss; with mult_dev == NULL loss and dpred are bit-identical to it.
+ *   kind 3, ratio of sums (ScaledGraphRELoss): loss = m / B * sum_g A_g / (T_g + 1e-8), A_g = sum of
+ *     |p' - t'| and T_g = sum of |t'| over the graph's n_g C elements; dpred = m / B * sign(p' - t') *
+ *     scale[c] / (T_g + 1e-8). eps is not used. A graph id without rows adds 0 / 1e-8 = 0, as the
+ *     torch expression.
+ *   kind 4, mixed (GraphMixedError): loss = m * (0.2 / B * sum_g Q_q(r over g) + 0.8 / B * sum_g mean
+ *     |p' - t'|), r = |p' - t'| / (|t'| + eps). Q_q as torch.quantile (linear): the rank q * (n - 1) in
+ *     f32 over the graph's n = n_g C elements, the two exact order statistics of ranks lo and lo + 1
+ *     by radix select, lerp in f32 with weight w = rank - lo; a NaN among the elements gives NaN (and
+ *     no quantile gradient). dpred: the dense gradient of the MAE term, plus 0.2 m / B * sign(p' - t')
+ *     * scale[c] / (|t'| + eps) times 1 - w at the element of rank lo and w at the one of rank lo + 1.
+ *     Ties: of several elements that hold a selected value, the one with the smallest flat index
+ *     i * C + c takes that value's whole weight; when ranks lo and lo + 1 hold the same value that one
+ *     element takes weight 1 (torch gives it to whichever elements its sort placed there, which it
+ *     does not specify).
+ *   kind 5, max component (GraphMaxComponentRelativeError): per graph and column c, i* = the row of
+ *     the largest |t'_c|, ties to the smallest row index (independent of the CSR's row order);
+ *     loss = m / (B C) * sum_g sum_c |p' - t'| / (|t'| + eps) at (i*, c); dpred is that term's
+ *     gradient at the B C selected elements and exactly 0 elsewhere (written by the kernel). Targets
+ *     must be finite.
+ * A graph id without rows makes the loss NaN for every kind but 3. The classes call kind 4 with
+ * m = 1, kind 5 with m = 10000, the force-scaled ones kinds 1, 2, 3 with mult = 100 and mult_dev from
+ * bgnn_force_scale. One workgroup per (graph, segment-block) for the sums and dense gradients, one
+ * per graph (1024 threads) for the select, one per graph for the maxima, a one-workgroup finish.
+ * ws: bgnn_graph_loss_ex_ws_bytes(N, C, B) bytes (any kind), 8-byte aligned. BGNN_E_ARG before
+ * anything is launched when: kind outside 0..5; C outside 1..8; N, N C or B outside [1, 2^31);
+ * kind 4 with q outside [0, 1]; pred, target, rowptr, col or loss NULL; ws NULL, misaligned or
+ * smaller than the query.
+ *
+ * bgnn_force_scale: out[0] = max(sum over rows r of ||x[r, c0 : c0 + nc]||_2, min_scale) for x
+ * [N, >= c0 + nc] with row stride ldx (ScaledGraph*Loss.compute_total_force and the max(.., min_scale)
+ * that follows it, Utils/Losses.py:519-524, 537), on the device. flag_col >= 0: rows whose
+ * x[r, flag_col] is non-zero are skipped (the super-node filter x[x[:, -1] == 0] of
+ * TRAIN_FINAL.py:256-260 without the mask gather); negative: every row counts. The row norm in f32
+ * (squares and sums rounded in column order, the root correctly rounded), the sum over rows in
+ * double in a fixed order, rounded once; a NaN total stays NaN. 1 <= nc <= 8. ws:
+ * bgnn_force_scale_ws_bytes(N) bytes, 8-byte aligned. BGNN_E_ARG before anything is launched when:
+ * N outside [1, 2^31); nc outside 1..8, c0 < 0 or c0 + nc > ldx; flag_col >= ldx; x or out NULL; ws
+ * NULL, misaligned or smaller than the query.
+ * ---------------------------------------------------------------------- */
+size_t bgnn_graph_loss_ex_ws_bytes(int64_t N, int32_t C, int64_t B);
+int bgnn_graph_loss_ex(const float* pred, const float* target, int64_t N, int32_t C, const int32_t* rowptr,
+                       const int32_t* col, int64_t B, int32_t kind, float eps, float mult, const float* scale,
+                       const float* center, float q, const float* mult_dev, float* loss, float* dpred, void* ws,
+                       size_t ws_bytes, void* stream);
+size_t bgnn_force_scale_ws_bytes(int64_t N);
+int bgnn_force_scale(const float* x, int64_t N, int64_t ldx, int32_t c0, int32_t nc, int32_t flag_col,
+                     float min_scale, float* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
