@@ -17,7 +17,7 @@ from .checkpoint import load_checkpoint, load_reference_checkpoint, save_checkpo
 from .dataset import load_dataset_cache
 from .inference import evaluate, evaluate_nodes
 from .train import ColumnScaler, EigenvalueScaler, GradAllReduce, RelativeErrorLoss, mape_error, train_step
-from .fused import node_head
+from .fused import node_head, node_head_bf16
 from . import losses
 from .losses import (GraphMAELoss, GraphMaxComponentRelativeError, GraphMixedError, GraphMSELoss,
                      GraphRelativeError, ScaledGraphMAELoss, ScaledGraphMSELoss, ScaledGraphRELoss, StressErrorMeter,
@@ -30,7 +30,7 @@ __all__ = [
     "install_pyg_shim", "uninstall_pyg_shim", "EigenvalueScaler", "GradAllReduce", "RelativeErrorLoss",
     "mape_error", "train_step", "load_library", "GraphStore", "load_checkpoint", "load_reference_checkpoint",
     "save_checkpoint", "load_dataset_cache", "evaluate", "losses", "GraphMAELoss", "GraphMaxComponentRelativeError", "GraphMixedError",
-    "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head",
+    "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head", "node_head_bf16",
     "evaluate_nodes", "StressErrorMeter", "graph_metrics", "ScaledGraphMAELoss", "ScaledGraphMSELoss",
     "ScaledGraphRELoss", "get_loss_function",
 ]

@@ -166,6 +166,7 @@ SIGNATURES = {
     "bgnn_head2_supported": (c_i32, [c_i32, c_i32, c_i32]),
     "bgnn_head2_geometry": (c_i32, [c_i32]),
     "bgnn_head2_fwd": (c_i32, [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "bgnn_head2_fwd_bf16": (c_i32, [c_p, c_i64, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     "bgnn_head2_bwd_ws_bytes": (c_sz, [c_i64, c_i32, c_i32]),
     "bgnn_head2_bwd": (c_i32, [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                c_sz, c_p]),

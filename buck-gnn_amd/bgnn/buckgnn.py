@@ -27,7 +27,8 @@ from . import ea as ea_mod
 from .ea import GradSlot as EAGradSlot, graphnet_block, skip_dropout
 from . import _lib
 from . import fused as _fused
-from .fused import RangeRows, mlp, mlp_bf16, node_head, prepare_weights, sage_layer, small_mlp
+from .fused import (RangeRows, mlp, mlp_bf16, node_head, node_head_bf16, node_head_bf16_accepts, prepare_weights,
+                    sage_layer, small_mlp)
 from .graph import SegmentIndex, graph_for, _index_cache
 from .nn import SAGEConv, SAGPooling, global_mean_pool, scatter_mean
 from .ops import segment_reduce
@@ -217,6 +218,13 @@ class BuckGNN(nn.Module):
         # "all": as True, and GraphSage_maxAggr too, on bf16 rows with a gather, a K = 2H GEMM and a
         # tail kernel per layer (fused.sage_infer_max_layer); under True a max model stays f32.
         self.infer_bf16 = False
+        # Node-level heads (static_disp / static_stress / mode_shape) where the bf16 inference loop
+        # above runs: the last layer stores bf16 too and the decoder reads those rows
+        # (fused.node_head_bf16: at h >= 256 its front Linear on one bf16 MFMA product with a bf16
+        # [N, 128] output, then bgnn_head2_fwd_bf16). Off: infer_bf16 hands the decoder f32 rows, as
+        # before. Everywhere else (buckling, train mode, a hooked decoder, N < 1024, a decoder shape
+        # node_head_bf16 declines, infer_bf16 off) the flag changes nothing. (_bf16_decoder_on)
+        self.infer_bf16_decoder = False
         # GraphSAGE sum / mean models (and GraphSage_addAggr_Shared) on the fused layer loop, training
         # included: the operands of every N-row Linear product rounded to bf16 and z = x [W_l;W_r]^T
         # stored as bf16, as torch.autocast(bf16) would; accumulators, normalize, BatchNorm, skip,
@@ -275,15 +283,33 @@ class BuckGNN(nn.Module):
         out = small_mlp(dec, h) if (self.use_fused and not hooked) else None
         return dec(h) if out is None else out
 
-    def _decode_nodes(self, x: Tensor) -> Optional[Tensor]:
+    def _decode_nodes(self, x: Tensor, rows_bf16: bool = False) -> Optional[Tensor]:
         """The node-level decoder on all N rows through bgnn.fused.node_head (the bgnn_head2 tail
         kernel, a bgnn GEMM in front at h >= 256) on the fused path from 1024 rows on (the fused
-        encoder's threshold); None where the torch modules run (hooks, few rows, other shapes)."""
+        encoder's threshold); None where the torch modules run (hooks, few rows, other shapes).
+        rows_bf16: x is the bf16 inference loop's bf16 output (_bf16_decoder_on held before the
+        loop): fused.node_head_bf16."""
         dec = self.decoder
+        if rows_bf16:
+            out = node_head_bf16(dec, x)
+            if out is None:   # (_bf16_decoder_on checked the decoder; the loop's rows are aligned)
+                raise RuntimeError("BuckGNN: node_head_bf16 declined the bf16 loop's rows")
+            return out
         hooked = bool(dec._forward_pre_hooks or dec._forward_hooks)
         if hooked or not self._fused_ok(x) or x.size(0) < 1024 or not isinstance(dec, nn.Sequential):
             return None
         return node_head(dec, x)
+
+    def _bf16_decoder_on(self, n_rows: int) -> bool:
+        """Whether the bf16 inference loop hands the node-level decoder bf16 rows
+        (infer_bf16_decoder); asked where that loop runs (_infer_bf16_on), before it: a node-level
+        head, an unhooked decoder of a shape fused.node_head_bf16 takes, and node_head's row
+        threshold."""
+        dec = self.decoder
+        return bool(getattr(self, "infer_bf16_decoder", False)
+                    and ("static" in self.prediction_type or "mode_shape" in self.prediction_type)
+                    and n_rows >= 1024 and not (dec._forward_pre_hooks or dec._forward_hooks)
+                    and node_head_bf16_accepts(dec))
 
     def _fused_ok(self, x: Tensor) -> bool:
         # float32 activations only: the fused kernels read f32 rows, so a bf16 activation (the
@@ -312,28 +338,30 @@ class BuckGNN(nn.Module):
         h = self.hidden_channels
         return bool(aggr in _bf16_aggrs(self.sage_bf16) and self._sage_fused(x, aggr) and h % 8 == 0 and h <= 512)
 
-    def _sage_loop_bf16(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, pool=None):
+    def _sage_loop_bf16(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, pool=None,
+                        out_bf16: bool = False):
         """The eval-mode SAGE layer loop on bf16 rows: per layer one bf16 GEMM and one aggregation +
-        tail kernel; the last layer writes f32 for the pooling and the decoder."""
+        tail kernel; the last layer writes f32 for the pooling and the decoder, or bf16 with
+        out_bf16 (the node-level decoder on bf16 rows, _bf16_decoder_on)."""
         L = len(convs) if convs is not None else self.num_layers
         graph = graph_for(edge_index, x.size(0))
         if aggr == "max":
-            x = self._sage_loop_bf16_max(x, graph, convs, bns, L)
+            x = self._sage_loop_bf16_max(x, graph, convs, bns, L, out_bf16)
             return (x, segment_reduce(x, pool, "mean")) if pool is not None else x
         red = 1 if aggr == "mean" else 0
         for i in range(L):
             conv = convs[i] if convs is not None else self.shared_graphsage_block
             coeffs = _fused.bn_eval_coeffs(bns[i]) if bns is not None else None
             x = _fused.sage_infer_layer(x, _fused.infer_weights(conv), conv.lin_l.bias, coeffs, graph, red,
-                                        x_prev=x if 0 < i < L - 1 else None, out_f32=i == L - 1)
+                                        x_prev=x if 0 < i < L - 1 else None, out_f32=i == L - 1 and not out_bf16)
         return (x, segment_reduce(x, pool, "mean")) if pool is not None else x
 
-    def _sage_loop_bf16_max(self, x: Tensor, graph, convs, bns, L: int) -> Tensor:
+    def _sage_loop_bf16_max(self, x: Tensor, graph, convs, bns, L: int, out_bf16: bool = False) -> Tensor:
         """The eval-mode max-aggregation layer loop on bf16 rows (infer_bf16 = "all"): max is not
         linear, so each layer aggregates first and transforms [agg | x] in one GEMM
         (fused.sage_infer_max_layer: gather, GEMM, tail). Two ping-pong [N, 2H] bf16 buffers hold
         [agg | x]: a layer's tail writes plane 1 of the other buffer, where the next layer's gather
-        reads it; the last layer writes f32 for the pooling and the decoder."""
+        reads it; the last layer writes f32 for the pooling and the decoder (bf16 with out_bf16)."""
         if L == 0:
             return x
         N, H = x.size(0), self.hidden_channels
@@ -346,10 +374,11 @@ class BuckGNN(nn.Module):
             coeffs = _fused.bn_eval_coeffs(bns[i]) if bns is not None else None
             cur = bufs[i % 2]
             last = i == L - 1
-            out = (torch.empty(N, H, dtype=torch.float32, device=x.device) if last
+            out = (torch.empty(N, H, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device) if last
                    else bufs[(i + 1) % 2][:, H:])
             _fused.sage_infer_max_layer(cur, _fused.infer_weights_max(conv), conv.lin_l.bias, coeffs, graph,
-                                        cur[:, H:] if 0 < i < L - 1 else None, out, out_f32=last, y=y)
+                                        cur[:, H:] if 0 < i < L - 1 else None, out, out_f32=last and not out_bf16,
+                                        y=y)
         return out
 
     def _foldable_encoder(self, x: Tensor) -> bool:
@@ -362,15 +391,17 @@ class BuckGNN(nn.Module):
                 and x.size(0) >= 1024 and self.num_layers >= 1)
 
     def _sage_loop(self, x: Tensor, edge_index: Tensor, convs, bns, aggr: str, skip_last_excluded: bool,
-                   x_amax: Optional[Tensor] = None, x_in: Optional[nn.Linear] = None, pool=None):
+                   x_amax: Optional[Tensor] = None, x_in: Optional[nn.Linear] = None, pool=None,
+                   out_bf16: bool = False):
         """The SAGE layer loop; pool (a SegmentIndex; fused sum / mean loop only): returns
         (x, mean pool of x per segment) from the last fused layer instead of x. The caller reads
         only the pool: the last fused layer sums it inside its apply pass and does not store x
-        (need_x=False; x is then None)."""
+        (need_x=False; x is then None). out_bf16 (the bf16 inference loop only): its last layer
+        stores bf16."""
         L = len(convs) if convs is not None else self.num_layers
         p = self.dropout.p
         if x_in is None and self._infer_bf16_on(x, aggr, bns):
-            return self._sage_loop_bf16(x, edge_index, convs, bns, aggr, pool)
+            return self._sage_loop_bf16(x, edge_index, convs, bns, aggr, pool, out_bf16)
         if self._sage_fused(x, aggr):
             graph = graph_for(edge_index, x.size(0))
             red = {"mean": 1, "max": 2}.get(aggr, 0)
@@ -485,6 +516,9 @@ class BuckGNN(nn.Module):
         sage_loop = name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"   # a _sage_loop model
         # the bf16 inference loop takes the encoder's f32 output: the encoder stays unfolded
         infer = sage_loop and self._infer_bf16_on(x, sage, self.batch_norms if name in _SAGE_VARIANTS else None)
+        # ... and hands the node-level decoder bf16 rows under infer_bf16_decoder (decided here, from
+        # the decoder's shapes: the loop's last layer then stores bf16)
+        dec16 = bool(infer and self.num_layers >= 1 and self._bf16_decoder_on(x.size(0)))
         # sage_bf16 keeps the encoder f32 and whole: folded, its last Linear would join layer 0's bf16
         # product (h and [W_l;W_r] W_in rounded instead of x0 and [W_l;W_r]: not autocast's points)
         unfold = sage_loop and self._sage_bf16_on(x, sage)
@@ -523,7 +557,7 @@ class BuckGNN(nn.Module):
             per_layer = name in _SAGE_VARIANTS
             convs = getattr(self, _SAGE_VARIANTS[name][0]) if per_layer else None
             bns = self.batch_norms if per_layer else None
-            x = self._sage_loop(x, edge_index, convs, bns, sage, True, x_amax, x_in, pool=pool)
+            x = self._sage_loop(x, edge_index, convs, bns, sage, True, x_amax, x_in, pool=pool, out_bf16=dec16)
             if pool is not None:
                 x, pooled = x
         elif name == "EA_GNN":
@@ -568,7 +602,7 @@ class BuckGNN(nn.Module):
                 pooled = self.get_pooling_layer(x, edge_index, batch)
             return self._decode(pooled).squeeze(), batch
         if "static" in self.prediction_type or "mode_shape" in self.prediction_type:
-            out = self._decode_nodes(x)
+            out = self._decode_nodes(x, dec16)
             if "super" in self.pooling_layer:
                 if out is not None:   # (row-independent decoder: the filter moves [N, C], not [N, H])
                     return out[is_real_node], real_node_batch

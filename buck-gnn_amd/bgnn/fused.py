@@ -584,13 +584,11 @@ class _Head2Fn(torch.autograd.Function):
 FUSED_NODE_HEAD = True
 
 
-def node_head(seq: torch.nn.Sequential, x: torch.Tensor):
-    """seq(x) for the node-level decoder: Linear(D0,64).ReLU.Linear(64,C) as one bgnn_head2 kernel
-    (h <= 128: the whole decoder), with a leading Linear.ReLU on the bgnn GEMM in front (h >= 256:
-    Linear(h,128).ReLU, bias and ReLU in the epilogue). None when seq is not of that form with f32
-    contiguous weights and biases, the shapes are not built (bgnn_head2_supported), or x is not a
-    float32 [N >= 1, in_features] GPU tensor."""
-    if not (FUSED_NODE_HEAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) > 0):
+def _head_linears(seq):
+    """The Linears of a node-level decoder that bgnn_head2 covers: seq is Linear.ReLU.Linear or
+    Linear.ReLU.Linear.ReLU.Linear with f32 contiguous GPU weights and biases, consecutive widths
+    agree and the last two Linears have a built shape (bgnn_head2_supported); else None."""
+    if not isinstance(seq, torch.nn.Sequential):
         return None
     mods = list(seq)
     want = (torch.nn.Linear, torch.nn.ReLU) * (len(mods) // 2) + (torch.nn.Linear,)
@@ -600,11 +598,26 @@ def node_head(seq: torch.nn.Sequential, x: torch.Tensor):
     if not all(m.weight.dtype == torch.float32 and m.weight.is_cuda and m.weight.is_contiguous() and m.bias is not None
                and m.bias.is_contiguous() for m in lins):
         return None
-    if x.size(1) != lins[0].in_features or any(a.out_features != b.in_features for a, b in zip(lins, lins[1:])):
+    if any(a.out_features != b.in_features for a, b in zip(lins, lins[1:])):
         return None
     l1, l2 = lins[-2:]
     if not _lib.query("bgnn_head2_supported", l1.in_features, l1.out_features, l2.out_features):
         return None
+    return lins
+
+
+def node_head(seq: torch.nn.Sequential, x: torch.Tensor):
+    """seq(x) for the node-level decoder: Linear(D0,64).ReLU.Linear(64,C) as one bgnn_head2 kernel
+    (h <= 128: the whole decoder), with a leading Linear.ReLU on the bgnn GEMM in front (h >= 256:
+    Linear(h,128).ReLU, bias and ReLU in the epilogue). None when seq is not of that form with f32
+    contiguous weights and biases, the shapes are not built (bgnn_head2_supported), or x is not a
+    float32 [N >= 1, in_features] GPU tensor."""
+    if not (FUSED_NODE_HEAD and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.size(0) > 0):
+        return None
+    lins = _head_linears(seq)
+    if lins is None or x.size(1) != lins[0].in_features:
+        return None
+    l1, l2 = lins[-2:]
     if len(lins) == 3:
         if lins[0].in_features % 4:
             return None
@@ -613,6 +626,61 @@ def node_head(seq: torch.nn.Sequential, x: torch.Tensor):
     if x.data_ptr() % 16:
         return None
     return _Head2Fn.apply(x, l1.weight, l1.bias, l2.weight, l2.bias)
+
+
+def head_front_weight(lin: torch.nn.Linear) -> torch.Tensor:
+    """The weight of the decoder's front Linear as node_head_bf16's GEMM reads it: rounded to bf16
+    once per weight version and kept on the module (as _cached_weights keeps a layer's), where the
+    bf16-weight kernel applies (b16_weight); else the f32 weight itself."""
+    w = lin.weight
+    if not (B16_WEIGHTS and w.size(1) % 64 == 0):
+        return w.detach()
+    key = (w._version, w.data_ptr(), str(w.device))
+    hit = getattr(lin, "_bgnn_head_w16", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        w16 = w.detach().to(torch.bfloat16).contiguous()
+    lin._bgnn_head_w16 = (key, w16)
+    return w16
+
+
+def node_head_bf16_accepts(seq) -> bool:
+    """Whether node_head_bf16 takes the decoder seq for bf16 rows of seq[0].in_features columns (the
+    conditions on seq alone: known before the rows exist)."""
+    lins = _head_linears(seq) if FUSED_NODE_HEAD else None
+    return lins is not None and lins[0].in_features % 8 == 0
+
+
+@torch.no_grad()
+def node_head_bf16(seq: torch.nn.Sequential, x: torch.Tensor):
+    """node_head on bfloat16 rows (eval-mode inference, no autograd): the tail is
+    bgnn_head2_fwd_bf16, which widens the bf16 rows exactly and then computes as bgnn_head2_fwd. With
+    two Linears (h = 64 or 128) it reads x in place, strided rows included; with three (h >= 256)
+    the front Linear.ReLU runs on gemm_bf16 -- bf16 A, the weight rounded to bf16 once
+    (head_front_weight), bias and ReLU in the epilogue, a bf16 [N, 128] output -- and the tail
+    reads that. Returns f32 [N, C]; None when seq is not node_head's form, or x is not a bfloat16
+    [N >= 1, in_features] GPU tensor with unit column stride and 16-byte aligned rows."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.size(0) > 0 and x.stride(1) == 1
+            and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0):
+        return None
+    if not node_head_bf16_accepts(seq):
+        return None
+    lins = _head_linears(seq)
+    if x.size(1) != lins[0].in_features:
+        return None
+    l1, l2 = lins[-2:]
+    if len(lins) == 3:
+        with _timed("head_front_bf16"):
+            x = gemm_bf16(x, head_front_weight(lins[0]), trans_a=False, trans_b=True, out_bf16=True,
+                          bias=lins[0].bias, relu=True)
+    N = x.size(0)
+    y = torch.empty(N, l2.out_features, dtype=torch.float32, device=x.device)
+    with _timed("head2_bf16"):
+        _lib.call("bgnn_head2_fwd_bf16", x.data_ptr(), x.stride(0), N, l1.in_features, l1.out_features,
+                  l2.out_features, l1.weight.data_ptr(), l1.bias.data_ptr(), l2.weight.data_ptr(),
+                  l2.bias.data_ptr(), y.data_ptr(), _stream())
+    return y
 
 
 def _mlp2_prefix(mods, x: torch.Tensor) -> bool:

@@ -67,7 +67,7 @@ def _evaluate(model, batches, normalizer, device) -> Dict[str, float]:
 
 @torch.no_grad()
 def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, threshold: Optional[float] = None,
-                   device=None) -> Dict[str, object]:
+                   device=None, bf16=None, return_predictions: bool = False) -> Dict[str, object]:
     """The static heads' evaluation (INFERENCE.py:153-172,189-199; the validation loop of
     TRAIN_FINAL.py:349-384): eval mode, no_grad, per batch the model's prediction and its returned
     (super-node adjusted) batch vector, stress_errors of the denormalised values accumulated in a
@@ -77,8 +77,31 @@ def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, th
     given.
     normalizer: a bgnn.ColumnScaler (folded into the metric kernel), a reference-style object with
     denormalize_displacement / denormalize_gp_stresses, or None.
+    bf16: None leaves the model's flags alone; True / "all" / False sets `infer_bf16` to that value
+    and `infer_bf16_decoder` to its truth value for this call (the bf16 layer loop with the decoder
+    on bf16 rows, BuckGNN.infer_bf16_decoder) and restores both after, as `evaluate` does.
+    return_predictions: also return the fields, not only their metrics.
     Returns {"metrics_per_graph": sums / graphs, "metrics_per_batch": sums / batches, "graphs",
-    "batches", "loss": the mean criterion value over batches or None}."""
+    "batches", "loss": the mean criterion value over batches or None}, and with return_predictions
+    "predictions": one (denormalised prediction [n, C], returned batch vector) per batch."""
+    if bf16 is None:
+        return _evaluate_nodes(model, batches, normalizer, criterion, threshold, device, return_predictions)
+    flags = {"infer_bf16": "all" if isinstance(bf16, str) and bf16 == "all" else bool(bf16),
+             "infer_bf16_decoder": bool(bf16)}
+    before = {k: vars(model)[k] for k in flags if k in vars(model)}
+    for k, v in flags.items():
+        setattr(model, k, v)
+    try:
+        return _evaluate_nodes(model, batches, normalizer, criterion, threshold, device, return_predictions)
+    finally:
+        for k in flags:
+            if k in before:
+                setattr(model, k, before[k])
+            else:
+                delattr(model, k)
+
+
+def _evaluate_nodes(model, batches, normalizer, criterion, threshold, device, return_predictions):
     from . import losses
     ptype = getattr(model, "prediction_type", "buckling")
     if ptype not in losses.METRIC_KEYS:
@@ -87,11 +110,14 @@ def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, th
     model.eval()
     meter = losses.StressErrorMeter(ptype, threshold)
     loss_sum = None
+    preds = []
     for batch in batches:
         if device is not None:
             batch = batch.to(device)
         prepare(batch.edge_index, batch.x.size(0), batch.batch, getattr(batch, "num_graphs", None) or None)
         pred, out_batch = model(batch.x, batch.edge_index, batch.edge_attr, batch.batch)
+        if return_predictions:
+            preds.append((_denormalize_nodes(normalizer, ptype, pred).detach(), out_batch))
         y = batch.y.contiguous() if ptype == "static_stress" else batch.y
         if normalizer is None or type(normalizer) is ColumnScaler:
             scale, center = normalizer._at(pred.device) if normalizer is not None else (None, None)
@@ -103,5 +129,8 @@ def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, th
             v = _node_criterion(model, batch, criterion, normalizer, pred, y, out_batch).detach().double()
             loss_sum = v if loss_sum is None else loss_sum + v
     graphs, n = meter.counts
-    return {"metrics_per_graph": meter.compute("graph"), "metrics_per_batch": meter.compute("batch"), "graphs": graphs,
-            "batches": n, "loss": float(loss_sum.item()) / n if loss_sum is not None else None}
+    out = {"metrics_per_graph": meter.compute("graph"), "metrics_per_batch": meter.compute("batch"), "graphs": graphs,
+           "batches": n, "loss": float(loss_sum.item()) / n if loss_sum is not None else None}
+    if return_predictions:
+        out["predictions"] = preds
+    return out

@@ -16,6 +16,10 @@
 // The backward recomputes the hidden layer from x with the same function (bit-identical to the
 // forward's) and accumulates dW1 / db1 / dW2 / db2 per workgroup; two kernels sum the
 // per-workgroup partials in a fixed order (no atomics: bit-identical from run to run).
+//
+// The forward also takes bf16 rows (bgnn_head2_fwd_bf16, eval-mode inference): only the x loader
+// differs, widening each bf16 exactly into the same fp32 tile, so y has the f32 entry's bits on
+// the widened rows.
 #include "common.h"
 
 namespace bgnn {
@@ -55,15 +59,33 @@ __device__ __forceinline__ void head_load_weights(HeadSmem<D0>& S, const float* 
     for (int i = threadIdx.x; i < kHCmax; i += kHeadThreads) S.b2[i] = (b2 && i < C) ? b2[i] : 0.f;
 }
 
-// the tile's x rows as float4 (x 16-byte aligned, D0 % 4 == 0); rows past N are zero
-template <int D0>
-__device__ __forceinline__ void head_load_x(HeadSmem<D0>& S, const float* x, int64_t n0, int64_t N) {
-    constexpr int F4 = D0 / 4;
-    for (int i = threadIdx.x; i < kHT * F4; i += kHeadThreads) {
-        const int n = i / F4, f = (i % F4) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n0 + n < N) v = ldf4(x + (n0 + n) * D0 + f);
-        *reinterpret_cast<float4*>(&S.xs[n][f]) = v;
+// a bf16 row element: the high half of the f32 it widens to
+struct HeadBf16 {
+    uint16_t bits;
+};
+
+// the tile's x rows in 16-byte vectors (x 16-byte aligned, row stride ldx elements a multiple of
+// the vector): 4 f32, or 8 bf16 widened exactly into the f32 tile; rows past N are zero
+template <int D0, typename T>
+__device__ __forceinline__ void head_load_x(HeadSmem<D0>& S, const T* x, int64_t ldx, int64_t n0, int64_t N) {
+    constexpr int V = 16 / (int)sizeof(T);
+    constexpr int G = D0 / V;
+    for (int i = threadIdx.x; i < kHT * G; i += kHeadThreads) {
+        const int n = i / G, f = (i % G) * V;
+        if constexpr (sizeof(T) == 4) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (n0 + n < N) v = ldf4(x + (n0 + n) * ldx + f);
+            *reinterpret_cast<float4*>(&S.xs[n][f]) = v;
+        } else {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (n0 + n < N) v = *reinterpret_cast<const uint4*>(x + (n0 + n) * ldx + f);
+            *reinterpret_cast<float4*>(&S.xs[n][f]) =
+                make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u),
+                            __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
+            *reinterpret_cast<float4*>(&S.xs[n][f + 4]) =
+                make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xffff0000u),
+                            __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xffff0000u));
+        }
     }
 }
 
@@ -104,10 +126,11 @@ __device__ __forceinline__ void head_hidden(HeadSmem<D0>& S) {
 
 // forward: after the hidden tile, thread e < 32 C owns element e of the tile's [32, C] output
 // block, which is contiguous in y: a wave stores one unbroken span
-template <int D0>
-__global__ __launch_bounds__(kHeadThreads) void k_head2_fwd(const float* __restrict__ x, int64_t N, const float* W1,
-                                                            const float* b1, const float* W2, const float* b2, int C,
-                                                            float* __restrict__ y) {
+// (T = float: ldx is D0, a constant at the call; T = HeadBf16: the caller's row stride)
+template <int D0, typename T>
+__global__ __launch_bounds__(kHeadThreads) void k_head2_fwd(const T* __restrict__ x, int64_t ldx, int64_t N,
+                                                            const float* W1, const float* b1, const float* W2,
+                                                            const float* b2, int C, float* __restrict__ y) {
     __shared__ HeadSmem<D0> S;
     head_load_weights<D0>(S, W1, b1, W2, b2, C);
     const int e = threadIdx.x;
@@ -116,7 +139,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_head2_fwd(const float* __restr
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int64_t n0 = t * kHT;
         __syncthreads();
-        head_load_x<D0>(S, x, n0, N);
+        head_load_x<D0>(S, x, sizeof(T) == 4 ? (int64_t)D0 : ldx, n0, N);
         __syncthreads();
         head_hidden<D0>(S);
         __syncthreads();
@@ -164,7 +187,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_head2_bwd(const float* __restr
     for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const int64_t n0 = t * kHT;
         __syncthreads();
-        head_load_x<D0>(S, x, n0, N);
+        head_load_x<D0>(S, x, (int64_t)D0, n0, N);
         {
             const int n = tid >> 3, c = tid & 7;
             S.gy[n][c] = (c < C && n0 + n < N) ? dy[(n0 + n) * C + c] : 0.f;
@@ -313,9 +336,34 @@ extern "C" int bgnn_head2_fwd(const float* x, int64_t N, int32_t D0, int32_t D1,
     const int blocks = head_blocks(N, kHeadFwdBlocks);
     hipStream_t s = as_stream(stream);
     if (D0 == 64)
-        hipLaunchKernelGGL((k_head2_fwd<64>), dim3(blocks), dim3(kHeadThreads), 0, s, x, N, W1, b1, W2, b2, (int)C, y);
+        hipLaunchKernelGGL((k_head2_fwd<64, float>), dim3(blocks), dim3(kHeadThreads), 0, s, x, (int64_t)64, N, W1, b1,
+                           W2, b2, (int)C, y);
     else
-        hipLaunchKernelGGL((k_head2_fwd<128>), dim3(blocks), dim3(kHeadThreads), 0, s, x, N, W1, b1, W2, b2, (int)C, y);
+        hipLaunchKernelGGL((k_head2_fwd<128, float>), dim3(blocks), dim3(kHeadThreads), 0, s, x, (int64_t)128, N, W1,
+                           b1, W2, b2, (int)C, y);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
+
+extern "C" int bgnn_head2_fwd_bf16(const void* x, int64_t ldx, int64_t N, int32_t D0, int32_t D1, int32_t C,
+                                   const float* W1, const float* b1, const float* W2, const float* b2, float* y,
+                                   void* stream) {
+    BGNN_REQUIRE(bgnn_head2_supported(D0, D1, C), "head2_bf16: shape %dx%dx%d not built (D0 64 or 128, D1 64, C 1..8)",
+                 D0, D1, C);
+    BGNN_REQUIRE(N >= 0, "head2_bf16: N < 0");
+    if (N == 0) return BGNN_OK;
+    BGNN_REQUIRE(x && W1 && W2 && y, "head2_bf16: null pointer");
+    BGNN_REQUIRE(aligned16(x), "head2_bf16: x must be 16-byte aligned");
+    BGNN_REQUIRE(ldx >= D0 && ldx % 8 == 0, "head2_bf16: ldx=%lld must be >= D0 and a multiple of 8", (long long)ldx);
+    const int blocks = head_blocks(N, kHeadFwdBlocks);
+    hipStream_t s = as_stream(stream);
+    const HeadBf16* xb = static_cast<const HeadBf16*>(x);
+    if (D0 == 64)
+        hipLaunchKernelGGL((k_head2_fwd<64, HeadBf16>), dim3(blocks), dim3(kHeadThreads), 0, s, xb, ldx, N, W1, b1, W2,
+                           b2, (int)C, y);
+    else
+        hipLaunchKernelGGL((k_head2_fwd<128, HeadBf16>), dim3(blocks), dim3(kHeadThreads), 0, s, xb, ldx, N, W1, b1, W2,
+                           b2, (int)C, y);
     BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }

@@ -954,6 +954,17 @@ int bgnn_head2_supported(int32_t D0, int32_t D1, int32_t C);
 int bgnn_head2_geometry(int32_t which);
 int bgnn_head2_fwd(const float* x, int64_t N, int32_t D0, int32_t D1, int32_t C, const float* W1,
                    const float* b1, const float* W2, const float* b2, float* y, void* stream);
+/* The forward on bf16 input rows (additive to ABI 22; eval-mode inference, no backward): x is
+ * bfloat16 [N, D0] with a row stride of ldx elements, ldx >= D0, ldx % 8 == 0, x 16-byte aligned
+ * (so every row starts on a 16-byte boundary: a column plane of a wider bf16 buffer qualifies);
+ * W1 / b1 / W2 / b2 fp32 as above, y fp32 [N, C] contiguous. Each bf16 is widened exactly (it is
+ * the high half of an f32) into the same fp32 tile, and the sums and their order are
+ * bgnn_head2_fwd's: for any input, y has the bits of bgnn_head2_fwd on the widened rows.
+ * BGNN_E_ARG for a shape bgnn_head2_supported declines, N < 0, a null x / W1 / W2 / y, an
+ * unaligned x, ldx < D0 or ldx % 8 != 0. N = 0: no launch, x and y may be NULL. */
+int bgnn_head2_fwd_bf16(const void* x, int64_t ldx, int64_t N, int32_t D0, int32_t D1, int32_t C,
+                        const float* W1, const float* b1, const float* W2, const float* b2, float* y,
+                        void* stream);
 size_t bgnn_head2_bwd_ws_bytes(int64_t N, int32_t D0, int32_t C);
 int bgnn_head2_bwd(const float* x, int64_t N, int32_t D0, int32_t D1, int32_t C, const float* W1,
                    const float* b1, const float* W2, const float* dy, float* dx, float* dW1, float* db1,
