@@ -7,7 +7,8 @@ include/bgnn.h). Importing the package does not touch the GPU.
 from . import _lib
 from .buckgnn import BuckGNN, GraphNetBlock, MLPPooling
 from .data import Batch, Data, DataLoader
-from .graph import Graph, SegmentIndex, clear_caches, graph_for, prepare, segments_for
+from .graph import (Graph, SegmentIndex, clear_caches, graph_for, prepare, readout_for, register_readout,
+                    segments_for)
 from .nn import (SAGEConv, SAGPooling, global_add_pool, global_max_pool, global_mean_pool, scatter_add, scatter_mean,
                  scatter_sum)
 from .ops import aggregate, segment_reduce
@@ -32,7 +33,7 @@ __all__ = [
     "save_checkpoint", "load_dataset_cache", "evaluate", "losses", "GraphMAELoss", "GraphMaxComponentRelativeError", "GraphMixedError",
     "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head", "node_head_bf16",
     "evaluate_nodes", "StressErrorMeter", "graph_metrics", "ScaledGraphMAELoss", "ScaledGraphMSELoss",
-    "ScaledGraphRELoss", "get_loss_function",
+    "ScaledGraphRELoss", "get_loss_function", "readout_for", "register_readout",
 ]
 
 

@@ -59,6 +59,7 @@ SIGNATURES = {
     "bgnn_store_gather_graph": (c_i32, [c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p,
                                         c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "bgnn_store_gather_rows": (c_i32, [c_p, c_i32, c_i32, c_i64, c_p, c_i64, c_p, c_p]),
+    "bgnn_readout_index": (c_i32, [c_p, c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
     "bgnn_get_tuning": (c_i32, [c_i32]),
     "bgnn_heavy_timing": (c_i32, [c_i32]),
     "bgnn_gemm_w_tile": (c_i32, [c_i64, c_i64, c_i64]),

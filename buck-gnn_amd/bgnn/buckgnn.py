@@ -29,7 +29,7 @@ from . import _lib
 from . import fused as _fused
 from .fused import (RangeRows, mlp, mlp_bf16, node_head, node_head_bf16, node_head_bf16_accepts, prepare_weights,
                     sage_layer, small_mlp)
-from .graph import SegmentIndex, graph_for, _index_cache
+from .graph import SegmentIndex, graph_for, readout_for, _index_cache
 from .nn import SAGEConv, SAGPooling, global_mean_pool, scatter_mean
 from .ops import segment_reduce
 
@@ -42,6 +42,13 @@ FOLD_ENCODER = True
 # per-graph mean pool (fused.SageLayerFn pool), so its backward reads the pooled gradient through
 # the batch vector instead of an [N, H] broadcast (A/B switch; the same bits)
 FUSED_POOL = True
+# buckling with a super-node or MLP readout, and the node-level heads' real-node filter, on a batch
+# whose readout index is registered (graph.readout_for; GraphStore.batch, register_readout): the last
+# fused sum / mean layer pools the 2B segments [real nodes | super node] per graph in its apply pass
+# and every readout is a view of that pool (BuckGNN._readout); "mlp" pools the batch segments the
+# same way. No mask, nonzero or per-step segment sort (A/B switch; the same bits)
+FUSED_READOUT = True
+_READOUT_MODES = ("mean_no_super", "supernode_only", "supernode_with_pooling", "mlp_no_super")
 # default of BuckGNN.sage_bf16 for models built afterwards: the fused sum / mean SAGE layer loop
 # with autocast's rounding points (BuckGNN._sage_bf16_on); "all": the max model too
 SAGE_BF16 = False
@@ -268,6 +275,23 @@ class BuckGNN(nn.Module):
         if mode == "mlp_no_super":
             return self.pooling_mpl(x[real], rb)
         raise ValueError(f"Unknown pooling layer: {mode}")
+
+    def _readout(self, pooled: Tensor) -> Tensor:
+        """The decoder's input from the last fused layer's pool (FUSED_READOUT). "mlp": pooled is
+        the batch segments' mean pool. The other modes: pooled is [2B, H] over the readout index,
+        row 2b the mean of graph b's real nodes and row 2b + 1 its super row, and each readout of
+        get_pooling_layer a view of it (autograd zero-fills the half a view does not read)."""
+        mode = self.pooling_layer
+        if mode == "mlp":
+            return self.pooling_mpl.mlp(pooled)
+        H = pooled.size(1)
+        if mode == "supernode_with_pooling":
+            return pooled.view(-1, 2 * H)
+        halves = pooled.view(-1, 2, H)
+        if mode == "supernode_only":
+            return halves[:, 1].contiguous()
+        mean = halves[:, 0].contiguous()
+        return self.pooling_mpl.mlp(mean) if mode == "mlp_no_super" else mean
 
     # ------------------------------------------------------------------ forward
     def _seed(self) -> int:
@@ -506,14 +530,18 @@ class BuckGNN(nn.Module):
 
     def forward(self, x, edge_index, edge_attr, batch=None, mask=None):
         name = self.model_name
-        if "super" in self.pooling_layer:
+        sage_loop = name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"   # a _sage_loop model
+        # the batch's registered readout index (FUSED_READOUT), where a _sage_loop model reads it
+        ro = (readout_for(batch) if (FUSED_READOUT and sage_loop and self.use_fused
+                                     and ("super" in self.pooling_layer or self.pooling_layer in _READOUT_MODES))
+              else None)
+        if "super" in self.pooling_layer and ro is None:
             is_real_node = x[:, -1] == 0 if x.size(1) > 0 else torch.ones(x.size(0), dtype=torch.bool,
                                                                            device=x.device)
             real_node_batch = batch[is_real_node] if batch is not None else None
         x_amax = None   # max|x| after the encoder (f16x3 operand scale of the first SAGE GEMM)
         x_in = None     # the encoder's last Linear when it is folded into the first SAGE layer
         sage = _SAGE_VARIANTS.get(name, (None, "add", None))[1]
-        sage_loop = name in _SAGE_VARIANTS or name == "GraphSage_addAggr_Shared"   # a _sage_loop model
         # the bf16 inference loop takes the encoder's f32 output: the encoder stays unfolded
         infer = sage_loop and self._infer_bf16_on(x, sage, self.batch_norms if name in _SAGE_VARIANTS else None)
         # ... and hands the node-level decoder bf16 rows under infer_bf16_decoder (decided here, from
@@ -548,10 +576,15 @@ class BuckGNN(nn.Module):
                 else:
                     x, e = self.shared_gn_block(x, edge_index, e)
                 x, e = self._skip_dropout(x, e, x_prev, e_prev, 0 < i < self.num_layers - 1, ea_fused)
-        # the buckling decoder's mean pool from the last fused sum / mean layer (FUSED_POOL)
-        pool = (batch_segments(batch) if (FUSED_POOL and self.prediction_type == "buckling"
-                                          and self.pooling_layer == "mean" and batch is not None and sage_loop
-                                          and self._sage_fused(x, sage) and sage != "max") else None)
+        # the buckling decoder's pool from the last fused sum / mean layer (FUSED_POOL, FUSED_READOUT)
+        pool = None
+        if (self.prediction_type == "buckling" and batch is not None and sage_loop and self._sage_fused(x, sage)
+                and sage != "max"):
+            mode = self.pooling_layer
+            if (FUSED_POOL and mode == "mean") or (FUSED_READOUT and mode == "mlp"):
+                pool = batch_segments(batch)
+            elif ro is not None and mode in _READOUT_MODES:
+                pool = ro.seg   # 2B segments: the real nodes and the super node of every graph
         pooled = None
         if sage_loop:   # (the Shared variant: one conv for every layer, no BatchNorm)
             per_layer = name in _SAGE_VARIANTS
@@ -560,6 +593,8 @@ class BuckGNN(nn.Module):
             x = self._sage_loop(x, edge_index, convs, bns, sage, True, x_amax, x_in, pool=pool, out_bf16=dec16)
             if pool is not None:
                 x, pooled = x
+                if self.pooling_layer != "mean":
+                    pooled = self._readout(pooled)
         elif name == "EA_GNN":
             if not ea_fused:
                 e = self.edge_encoder(edge_attr)
@@ -604,6 +639,10 @@ class BuckGNN(nn.Module):
         if "static" in self.prediction_type or "mode_shape" in self.prediction_type:
             out = self._decode_nodes(x, dec16)
             if "super" in self.pooling_layer:
+                if ro is not None:   # the real nodes by the readout index: no mask, no nonzero
+                    if out is not None:
+                        return out.index_select(0, ro.real_index), ro.real_batch
+                    return self.decoder(x.index_select(0, ro.real_index)), ro.real_batch
                 if out is not None:   # (row-independent decoder: the filter moves [N, C], not [N, H])
                     return out[is_real_node], real_node_batch
                 return self.decoder(x[is_real_node]), real_node_batch

@@ -14,6 +14,7 @@ import ctypes
 from dataclasses import dataclass, field
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -292,7 +293,7 @@ class _Cache:
 
 
 _graph_cache = _Cache()
-_index_cache = _Cache()
+_index_cache = _Cache(16)   # (a super-node store batch holds three entries: batch, readout, real nodes)
 _empty_csrs = {}
 
 
@@ -342,6 +343,129 @@ def graph_for(edge_index: torch.Tensor, num_nodes: int, chunk: int = DEFAULT_CHU
 def segments_for(index: torch.Tensor, num_rows: int, chunk: int = DEFAULT_CHUNK) -> SegmentIndex:
     return _index_cache.get(index, (int(num_rows), chunk),
                             lambda: SegmentIndex.build(index, num_rows, chunk))
+
+
+def host_plan_pack(rowptr_h, chunk: int):
+    """The heavy-row plan of a CSR whose rowptr the host holds, as one int32 array
+    [heavy rows ascending | heavy_chunk0 = running chunk counts | chunk -> heavy row] -- what
+    bgnn_heavy_plan writes -- with the two counts: (pack, n_heavy, n_chunks); an empty pack when no
+    row has more than `chunk` entries."""
+    deg = np.diff(np.asarray(rowptr_h, dtype=np.int64))
+    heavy = np.nonzero(deg > chunk)[0]
+    if heavy.size == 0:
+        return np.zeros(0, dtype=np.int32), 0, 0
+    nch = (deg[heavy] + chunk - 1) // chunk
+    c0 = np.concatenate([[0], np.cumsum(nch)])
+    ch = np.repeat(np.arange(heavy.size), nch)
+    return np.concatenate([heavy, c0, ch]).astype(np.int32), int(heavy.size), int(c0[-1])
+
+
+def plan_of_pack(d: Optional[torch.Tensor], h: int, n_chunks: int, chunk: int, none: torch.Tensor) -> Plan:
+    """The Plan over an uploaded host_plan_pack (d: device int32); none: the int32 placeholder (two
+    zeros) of a plan without heavy rows."""
+    if h == 0:
+        return Plan(none, none, none, 0, 0, chunk)
+    return Plan(d[:h], d[h:2 * h + 1], d[2 * h + 1:2 * h + 1 + n_chunks], h, n_chunks, chunk)
+
+
+def host_plan(rowptr_h, chunk: int, device, none: Optional[torch.Tensor] = None) -> Plan:
+    """Heavy-row plan of a CSR whose rowptr the host holds (pooling segments: a row per graph),
+    computed in numpy (host_plan_pack) and uploaded in one pinned copy. none: the int32 placeholder
+    of a plan without heavy rows (two zeros; made here when not given)."""
+    pack, h, n_chunks = host_plan_pack(rowptr_h, chunk)
+    if h == 0:
+        return plan_of_pack(None, 0, 0, chunk,
+                            none if none is not None else torch.zeros(2, dtype=torch.int32, device=device))
+    d = torch.from_numpy(pack).pin_memory().to(device, non_blocking=True)
+    return plan_of_pack(d, h, n_chunks, chunk, none)
+
+
+def readout_rowptrs(n_nodes):
+    """Host rowptrs of a super-node batch's readout segments from its per-graph node counts: the 2B
+    segments [real nodes | super node] per graph (as bgnn_readout_index writes rowptr2) and the B
+    real-node segments."""
+    n_nodes = np.asarray(n_nodes, dtype=np.int64)
+    B = n_nodes.size
+    dn = np.concatenate([[0], np.cumsum(n_nodes)])
+    rp2 = np.empty(2 * B + 1, dtype=np.int64)
+    rp2[0::2], rp2[1::2] = dn, dn[1:] - 1
+    return rp2, dn - np.arange(B + 1)
+
+
+@dataclass
+class Readout:
+    """The readout index of a batch whose graphs each end in their super node
+    (VirtualEdgeCreate.py:106-107), from one bgnn_readout_index launch. seg: the SegmentIndex of 2B
+    segments [real nodes of graph 0 | super node of graph 0 | real nodes of graph 1 | ...] over the N
+    rows, each listed once: the pool bgnn_sage_apply_pool takes, whose even rows are the real-node
+    means and odd rows the super rows. real_index / real_batch: the real nodes' rows and graphs;
+    real_seg: the SegmentIndex of real_batch (B segments), also in _index_cache under real_batch."""
+
+    seg: SegmentIndex
+    real_index: torch.Tensor
+    real_batch: torch.Tensor
+    real_seg: SegmentIndex
+
+
+def build_readout(batch: torch.Tensor, ptr: torch.Tensor, n_nodes, chunk: int = DEFAULT_CHUNK, arange=None,
+                  none: Optional[torch.Tensor] = None, plans=None) -> Readout:
+    """Build and register the readout index of `batch` (Readout; readout_for finds it). ptr: the
+    batch's device int64 [B + 1]; n_nodes: the host's per-graph node counts, from which the
+    heavy-segment plans come (host_plan over readout_rowptrs): no sort and no read-back.
+    arange(n): an int32 device arange of at least n elements (a cache; a fresh one when None).
+    plans: the two plans (2B segments, real-node segments) where the caller uploaded them already."""
+    require_cuda(batch, ptr, what="build_readout")
+    n_nodes = np.asarray(n_nodes, dtype=np.int64)
+    B = int(n_nodes.size)
+    if B == 0 or int(n_nodes.min()) < 1:
+        raise ValueError("build_readout: every graph needs at least its super node")
+    dn = np.concatenate([[0], np.cumsum(n_nodes)])
+    N = int(dn[-1])
+    if batch.numel() != N or ptr.numel() != B + 1:
+        raise ValueError("build_readout: batch / ptr do not match the node counts")
+    dev = batch.device
+    ptr = ptr.to(torch.int64).contiguous()
+    rowptr2 = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)
+    seg_of_row = torch.empty(N, dtype=torch.int64, device=dev)
+    real_index = torch.empty(N - B, dtype=torch.int64, device=dev)
+    real_batch = torch.empty(N - B, dtype=torch.int64, device=dev)
+    real_rowptr = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    _lib.call("bgnn_readout_index", ptr.data_ptr(), B, N, int(n_nodes.min()), int(n_nodes.max()), rowptr2.data_ptr(),
+              seg_of_row.data_ptr(), _ptr(real_index) if N > B else None, _ptr(real_batch) if N > B else None,
+              real_rowptr.data_ptr(), _stream())
+    if arange is None:
+        ar = torch.arange(N + 1, dtype=torch.int32, device=dev)
+        arange = lambda n: ar   # noqa: E731
+    z = none if none is not None else torch.zeros(2, dtype=torch.int32, device=dev)
+    if plans is None:
+        plans = [host_plan(rp, chunk, dev, z) for rp in readout_rowptrs(n_nodes)]
+    empty = Plan(z, z, z, 0, 0, chunk)   # (a transpose has one entry per row: no heavy rows)
+    seg = SegmentIndex(N, 2 * B, Csr(rowptr2, arange(N), 2 * B, N, plans[0]),
+                       Csr(arange(N + 1), seg_of_row.to(torch.int32), N, N, empty), seg_of_row, None)
+    real_seg = SegmentIndex(N - B, B, Csr(real_rowptr, arange(N - B), B, N - B, plans[1]),
+                            Csr(arange(N - B + 1), real_batch.to(torch.int32) if N > B else z, N - B, N - B, empty),
+                            real_batch, None)
+    ro = Readout(seg, real_index, real_batch, real_seg)
+    _index_cache.put(batch, ("readout",), ro)
+    _index_cache.put(real_batch, ("batch",), real_seg)
+    return ro
+
+
+def readout_for(batch: Optional[torch.Tensor]) -> Optional[Readout]:
+    """The readout index registered for this batch vector (GraphStore.batch on a super-node store,
+    register_readout), or None: the models then take the path without it."""
+    return None if batch is None else _index_cache.peek(batch, ("readout",))
+
+
+def register_readout(batch: torch.Tensor, ptr: torch.Tensor, chunk: int = DEFAULT_CHUNK) -> Readout:
+    """Register the readout index of a host-collated super-node batch (data.Batch: batch.batch,
+    batch.ptr): one read-back of ptr per distinct batch tensor, as batch_segments costs. The caller
+    vouches that every graph's last node is its super node and no other node is one."""
+    ro = readout_for(batch)
+    if ro is None:
+        p = ptr.detach().to("cpu", torch.int64).numpy()
+        ro = build_readout(batch, ptr.to(batch.device), p[1:] - p[:-1], chunk)
+    return ro
 
 
 def clear_caches() -> None:

@@ -64,6 +64,9 @@ class GraphStore:
         self.n_nodes, self.n_edges = n, e
         self.node_off = np.concatenate([[0], np.cumsum(n)])
         self.edge_off = np.concatenate([[0], np.cumsum(e)])
+        # every graph ends in its super node and has no other (VirtualEdgeCreate.py:106-107): batches
+        # then carry the readout index (graph.Readout); checked once, here, on the host
+        self.super_nodes = self._has_super_nodes(graphs, n)
 
         # classify attributes like PyG collation
         keys: List[str] = []
@@ -137,6 +140,18 @@ class GraphStore:
         self.heavy = heavy.cpu().numpy()          # per graph: fwd heavy rows, fwd chunks, bwd rows, bwd chunks
         self._ptr_cache: Dict[int, torch.Tensor] = {}
 
+    def _has_super_nodes(self, graphs, n) -> bool:
+        """Whether the last feature column of x (the super-node flag) is non-zero at the last node
+        of every graph and zero at every other node."""
+        xs = [d._store.get("x") for d in graphs]
+        if int(n.min()) < 1 or not all(isinstance(x, torch.Tensor) and x.dim() == 2 and x.size(1) > 0
+                                       and x.size(0) == k for x, k in zip(xs, n)):
+            return False
+        flag = torch.cat([x[:, -1] for x in xs]).cpu().numpy() != 0
+        want = np.zeros(flag.size, dtype=bool)
+        want[self.node_off[1:] - 1] = True
+        return bool(np.array_equal(flag, want))
+
     def _build_group(self, graphs, g0, g1, ei_l, heavy):
         dev = self.device
         n0, n1 = int(self.node_off[g0]), int(self.node_off[g1])
@@ -207,6 +222,11 @@ class GraphStore:
         # [table (B x 6) | graph ids (B) | ptr (B + 1) | group table (B x 7, when planned)]
         gt = self._group_table(ids, dn, de, ne)
         parts = [table.reshape(-1), ids, dn] + ([gt.reshape(-1)] if gt is not None else [])
+        # ... and, on a super-node store, the heavy-segment plans of the readout index (int32 pairs)
+        ro_packs = [_graph.host_plan_pack(rp, self.chunk) for rp in _graph.readout_rowptrs(nn_)] \
+            if self.super_nodes else []
+        n_fixed = len(parts)
+        parts += [np.concatenate([p, np.zeros(len(p) % 2, dtype=np.int32)]).view(np.int64) for p, _, _ in ro_packs]
         offs, n = [], 0
         for a in parts:   # each part starts 16-B aligned on the device
             offs.append(n)
@@ -268,6 +288,13 @@ class GraphStore:
                                     torch.zeros(1, dtype=torch.int32, device=dev), 0, 0, self.chunk)
         seg_b = Csr(self._arange(Nb + 1), batch.to(torch.int32), Nb, Nb, self._empty_plan)
         _index_cache.put(batch, ("batch",), SegmentIndex(Nb, B, seg_f, seg_b, batch, None))
+        if self.super_nodes:
+            # readout index of a super-node batch (graph.Readout): one launch, the plans from the host
+            # counts inside the upload above, every identity col a prefix of the one cached arange
+            z = self._zeros_i32()
+            plans = [_graph.plan_of_pack(up[o:o + len(a)].view(torch.int32), h, c, self.chunk, z)
+                     for o, a, (_, h, c) in zip(offs[n_fixed:], parts[n_fixed:], ro_packs)]
+            _graph.build_readout(batch, ptr, nn_, self.chunk, lambda n: self._arange(Nb + 1), z, plans)
         return out
 
     def _group_table(self, ids, dn, de, ne):
@@ -320,20 +347,8 @@ class GraphStore:
 
     def _plan_host(self, rowptr_h: np.ndarray) -> Plan:
         """Heavy-row plan of a CSR whose rowptr the host holds (the pooling segments: one row per
-        graph), computed in numpy and uploaded in one copy -- the same arrays bgnn_heavy_plan
-        writes: heavy rows ascending, heavy_chunk0 = running chunk counts, chunk -> heavy row."""
-        deg = np.diff(np.asarray(rowptr_h, dtype=np.int64))
-        heavy = np.nonzero(deg > self.chunk)[0]
-        if heavy.size == 0:
-            z = self._zeros_i32()
-            return Plan(z, z, z, 0, 0, self.chunk)
-        nch = (deg[heavy] + self.chunk - 1) // self.chunk
-        c0 = np.concatenate([[0], np.cumsum(nch)])
-        ch = np.repeat(np.arange(heavy.size), nch)
-        pack = torch.from_numpy(np.concatenate([heavy, c0, ch]).astype(np.int32)).pin_memory()
-        d = pack.to(self.device, non_blocking=True)
-        h = heavy.size
-        return Plan(d[:h], d[h:2 * h + 1], d[2 * h + 1:], int(h), int(c0[-1]), self.chunk)
+        graph): graph.host_plan with the store's chunk and its shared placeholder."""
+        return _graph.host_plan(rowptr_h, self.chunk, self.device, self._zeros_i32())
 
     def _zeros_i32(self) -> torch.Tensor:
         z = self._ptr_cache.get("zeros")

@@ -114,6 +114,43 @@ __global__ __launch_bounds__(256) void k_store_rows4(const int64_t* __restrict__
         o[i] = a[i];
 }
 
+// Readout tables of a super-node batch (bgnn_readout_index): graph b owns rows [ptr[b], ptr[b+1])
+// and its last row is the super node. grid (x, B): blockIdx.y = graph, one thread per node of it.
+// ptr is device data the launcher cannot see: a range is clipped to [0, N] and a real-node slot to
+// [0, N - B), so a ptr that is not this batch's writes wrong tables but nothing out of bounds.
+__global__ __launch_bounds__(256) void k_readout_index(const int64_t* __restrict__ ptr, int B, int64_t N,
+                                                       int32_t* __restrict__ rowptr2,
+                                                       int64_t* __restrict__ seg_of_row,
+                                                       int64_t* __restrict__ real_index,
+                                                       int64_t* __restrict__ real_batch,
+                                                       int32_t* __restrict__ real_rowptr) {
+    const int b = blockIdx.y;
+    int64_t p0 = ptr[b], p1 = ptr[b + 1];
+    p0 = p0 < 0 ? 0 : (p0 > N ? N : p0);
+    p1 = p1 < p0 ? p0 : (p1 > N ? N : p1);
+    const int64_t nn = p1 - p0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t i = t0; i < nn; i += stride) {
+        const bool sup = i == nn - 1;
+        seg_of_row[p0 + i] = 2 * (int64_t)b + (sup ? 1 : 0);
+        const int64_t r = p0 - b + i;   // real nodes in order: one super node per earlier graph
+        if (!sup && r >= 0 && r < N - B) {
+            real_index[r] = p0 + i;
+            real_batch[r] = b;
+        }
+    }
+    if (t0 == 0) {
+        rowptr2[2 * b] = (int32_t)p0;
+        rowptr2[2 * b + 1] = (int32_t)(nn > 0 ? p1 - 1 : p0);
+        real_rowptr[b] = (int32_t)(p0 - b);
+        if (b == B - 1) {
+            rowptr2[2 * B] = (int32_t)N;
+            real_rowptr[B] = (int32_t)(N - B);
+        }
+    }
+}
+
 inline unsigned blocks_for(int64_t work, int B) {
     // ~2048 workgroups in total across the batch
     int64_t per = (2048 + B - 1) / B;
@@ -164,6 +201,23 @@ extern "C" int bgnn_store_gather_groups(const int64_t* gtable, int32_t B, int32_
     hipLaunchKernelGGL(k_store_groups, dim3(blocks_for(work, B), B), dim3(256), 0, as_stream(stream), gtable, B,
                        group_rows, Nb, Gb, gsrc, gmask, gcnt, gsrc_t, gmask_t, gcnt_t, gsrc_out, gmask_out, gcnt_out,
                        gsrc_t_out, gmask_t_out, gcnt_t_out, grow_out);
+    BGNN_CHECK_LAUNCH();
+    return BGNN_OK;
+}
+
+extern "C" int bgnn_readout_index(const int64_t* ptr, int32_t B, int64_t N, int64_t min_nodes, int64_t max_nodes,
+                                  int32_t* rowptr2, int64_t* seg_of_row, int64_t* real_index, int64_t* real_batch,
+                                  int32_t* real_rowptr, void* stream) {
+    BGNN_REQUIRE(B >= 1 && B <= 65535, "readout_index: batch of %d graphs unsupported", B);
+    BGNN_REQUIRE(N >= B && N < (int64_t(1) << 31), "readout_index: N %lld out of range for %d graphs", (long long)N,
+                 B);
+    BGNN_REQUIRE(min_nodes >= 1, "readout_index: a graph with fewer than 1 node has no super node");
+    BGNN_REQUIRE(max_nodes >= min_nodes && max_nodes <= N, "readout_index: max_nodes %lld out of range",
+                 (long long)max_nodes);
+    BGNN_REQUIRE(ptr && rowptr2 && seg_of_row && real_rowptr, "readout_index: null pointer");
+    BGNN_REQUIRE(N == B || (real_index && real_batch), "readout_index: null real-node arrays");
+    hipLaunchKernelGGL(k_readout_index, dim3(blocks_for(max_nodes, B), B), dim3(256), 0, as_stream(stream), ptr, B, N,
+                       rowptr2, seg_of_row, real_index, real_batch, real_rowptr);
     BGNN_CHECK_LAUNCH();
     return BGNN_OK;
 }

@@ -825,6 +825,25 @@ int bgnn_store_gather_groups(const int64_t* gtable, int32_t B, int32_t group_row
  * row-major store array (row_bytes per row, a multiple of 4) into the batch array. */
 int bgnn_store_gather_rows(const int64_t* table, int32_t B, int32_t per_edge, int64_t max_rows,
                            const void* src, int64_t row_bytes, void* dst, void* stream);
+/* Readout tables of a super-node batch, one launch (additive at ABI 22). ptr: device int64 [B + 1],
+ * graph b owns rows [ptr[b], ptr[b+1]) of the N and its last row is the super node
+ * (VirtualEdgeCreate.py:106-107). min_nodes / max_nodes: the smallest and largest graph, known to
+ * the host (the check below and the launch geometry). Outputs:
+ *   rowptr2     int32 [2B + 1]  {ptr[0], ptr[1]-1, ptr[1], ptr[2]-1, ..., ptr[B]}: the CSR (identity
+ *                               col) of 2B segments, real nodes of graph b = segment 2b, its super
+ *                               node = segment 2b + 1; every row is listed once, as
+ *                               bgnn_sage_apply_pool requires of its pool
+ *   seg_of_row  int64 [N]       2b or 2b + 1: each row's segment
+ *   real_index  int64 [N - B]   the real nodes' rows, ascending
+ *   real_batch  int64 [N - B]   their graphs
+ *   real_rowptr int32 [B + 1]   ptr[b] - b: the real nodes' segments per graph
+ * A graph of one node has an empty real segment. BGNN_E_ARG, before anything is launched, when:
+ * B < 1 or B > 65535; N < B or N >= 2^31; min_nodes < 1; max_nodes < min_nodes or > N; ptr,
+ * rowptr2, seg_of_row or real_rowptr is NULL; real_index or real_batch is NULL with N > B. A ptr
+ * that is not the batch's gives wrong tables, never a write outside them. */
+int bgnn_readout_index(const int64_t* ptr, int32_t B, int64_t N, int64_t min_nodes, int64_t max_nodes,
+                       int32_t* rowptr2, int64_t* seg_of_row, int64_t* real_index, int64_t* real_batch,
+                       int32_t* real_rowptr, void* stream);
 
 /* ------------------------------------------------------------------------
  * SAGPooling (torch_geometric.nn.SAGPooling as the reference builds it for GraphSAGE_SAG /
