@@ -66,7 +66,9 @@ __device__ __forceinline__ void h3p_wait(H3pA<NU>& r) {
 // epilogue
 // 8 waves (128 x 256, one workgroup per CU) or 4 waves (128 x 128, MINB = 2 workgroups per CU,
 // whose epilogues and barriers then overlap the other's main loop)
-template <int BM, int BN, int WM, int WN, int NSB, int ABL, int X = 0, int MINB = 1>
+// RS = 1: x6_epilogue and the LDS-source drop-add epilogue below store C in whole row segments of
+// the wave tile (knob BGNN_TUNE_GEMM_CSTORE)
+template <int BM, int BN, int WM, int WN, int NSB, int ABL, int X = 0, int MINB = 1, int RS = 0>
 __global__ __launch_bounds__(64 * WM * WN, MINB) void k_gemm_h3p(GemmArgs g) {
     constexpr int NT = 64 * WM * WN;
     static_assert(WM * WN == 8 || WM * WN == 4, "8 or 4 waves");
@@ -293,6 +295,45 @@ __global__ __launch_bounds__(64 * WM * WN, MINB) void k_gemm_h3p(GemmArgs g) {
             const float iab = ia * ib;
             const bool one_mul = fastw && iab != 0.f && iab < 3.0e38f;
             const float* bl = reinterpret_cast<const float*>(bslots);
+            if constexpr (RS != 0) {
+                // row segments: one 16-row block across the wave's TN * 32 columns at a time (the same
+                // 4 KiB stage; x6_stage_write_rows' layout), each row stored as one contiguous segment
+                // -- 4 rows x 256 B per wave instruction; the source rows read from LDS the same way
+                constexpr int RW = TN * 32, LPR = 8 * TN, RPI = 64 / LPR, NQ = 16 / RPI;
+                static_assert(16 * RW <= 1024 && 64 % LPR == 0, "a 16-row block fits the wave's 4 KiB stage");
+                const int rl = lane / LPR, cl = (lane % LPR) * 4;
+                const int tcol = wn * (BN / WN) + cl;
+                const int64_t col = n0 + tcol;
+#pragma unroll
+                for (int ii = 0; ii < 2 * TM; ++ii) {
+                    x6_stage_write_rows<TM, TN>(stg, acc, ii, lane);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const int rr = q * RPI + rl;
+                        const int trow = wm * (BM / WM) + ii * 16 + rr;   // row in the tile
+                        const int64_t row = m0 + trow;
+                        const float4 sv = *reinterpret_cast<const float4*>(stg + rr * RW + x6_rows_col(rr, cl));
+                        const float4 src = *reinterpret_cast<const float4*>(
+                            bl + (int)((nk + trow / (BM / NSB)) % NSB) * (B_U4 * 4) + (trow % (BM / NSB)) * BN + tcol);
+                        if (row >= g.M) continue;
+                        float pv[4];
+                        beta_mask4(g, row, col, src, pv);
+                        const float e[4] = {sv.x, sv.y, sv.z, sv.w};
+                        float o[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            float v = one_mul ? e[k] * iab : (e[k] * ia) * ib;
+                            v *= g.alpha;
+                            v += g.beta * pv[k];
+                            o[k] = v;
+                        }
+                        st_nt4(g.C + row * g.ldc + col, o);
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
+                return;
+            }
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -337,10 +378,10 @@ __global__ __launch_bounds__(64 * WM * WN, MINB) void k_gemm_h3p(GemmArgs g) {
     if (ABL == 8 && n0 < g.bsrc_c0) {   // drop-add GEMM, a column tile left of the beta operand
         GemmArgs ge = g;
         ge.beta = 0.f;
-        x6_epilogue<TM, TN, ABL, false>(ge, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, 0, lane, ia, ib, stage);
+        x6_epilogue<TM, TN, ABL, false, RS != 0>(ge, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, 0, lane, ia, ib, stage);
         return;
     }
-    x6_epilogue<TM, TN, ABL, false>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, 0, lane, ia, ib, stage);
+    x6_epilogue<TM, TN, ABL, false, RS != 0>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, 0, lane, ia, ib, stage);
 }
 
 
@@ -395,6 +436,16 @@ void launch_h3p(int cfg, int abl, dim3 grid, hipStream_t s, const GemmArgs& g) {
         return;
     }
 #endif
+    if (g_x6_rowseg) {   // (knob 17: the row-segment C stores)
+        if (abl == 8) {
+            if (g_h3p_nsb == 4) hipLaunchKernelGGL((k_gemm_h3p<128, 256, 2, 4, 4, 8, 0, 1, 1>), grid, dim3(512), 0, s, g);
+            else hipLaunchKernelGGL((k_gemm_h3p<128, 256, 2, 4, 3, 8, 0, 1, 1>), grid, dim3(512), 0, s, g);
+        } else {
+            if (g_h3p_nsb == 4) hipLaunchKernelGGL((k_gemm_h3p<128, 256, 2, 4, 4, 0, 0, 1, 1>), grid, dim3(512), 0, s, g);
+            else hipLaunchKernelGGL((k_gemm_h3p<128, 256, 2, 4, 3, 0, 0, 1, 1>), grid, dim3(512), 0, s, g);
+        }
+        return;
+    }
     if (abl == 8) {
         if (g_h3p_nsb == 4) hipLaunchKernelGGL((k_gemm_h3p<128, 256, 2, 4, 4, 8>), grid, dim3(512), 0, s, g);
         else hipLaunchKernelGGL((k_gemm_h3p<128, 256, 2, 4, 3, 8>), grid, dim3(512), 0, s, g);

@@ -1,6 +1,8 @@
 // Split-precision GEMM tile helpers of gemm_x6.hip (and the bf16 C stores gemm_b16.hip shares):
 // operand piece splits, the f16x3 operand scale and the LDS-staged C epilogue.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "gemm_common.h"
 
@@ -98,7 +100,27 @@ __device__ __forceinline__ void x6_stage_write(float* __restrict__ stage, const 
                     stage[(i * 32 + si * 16 + 4 * lq + r) * 32 + sj * 16 + l16] = acc[2 * i + si][2 * j + sj][r];
 }
 
-template <int TM, int TN, int ABL = 0, bool C16 = false, typename Acc>
+// Row-segment stage (x6_epilogue<ROWS>): 16-row block ii of the wave tile across all of its
+// TN * 32 columns, [16][TN*32] f32 -- acc[ii][0 .. 2 TN) as the 16x16x32 C/D map holds it (row = 4 (lane >> 4) + r,
+// col = 16 jj + (lane & 15)), no register shuffles. Rows of odd (row >> 2) keep their two 16-column
+// halves of each 32 swapped (column ^ 16): the lanes of one ds_write_b32 group (lane >> 4 = 0, 1 or
+// 2, 3) would otherwise hit the same 16 banks 4 rows = 4 TN * 32 floats apart; swapped they cover
+// all 32. The read-back (x6_rows_col) takes whole rows, 8 TN lanes per row: every 16-lane
+// ds_read_b128 group reads 64 distinct banks, as any group of rows with equal (row >> 2) & 1 does.
+// (checked for TN = 1, 2, 4 against the group / bank table of the LDS: tools/lds_banks.py)
+template <int TM, int TN>
+__device__ __forceinline__ void x6_stage_write_rows(float* __restrict__ stage, const floatx4 (&acc)[2 * TM][2 * TN],
+                                                    int ii, int lane) {
+    const int l16 = lane & 15, lq = lane >> 4, sw = (lq & 1) * 16;
+#pragma unroll
+    for (int jj = 0; jj < 2 * TN; ++jj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) stage[(4 * lq + r) * (TN * 32) + ((jj * 16) ^ sw) + l16] = acc[ii][jj][r];
+}
+// stage column of wave-tile column c (a multiple of 4) in row rr of the block
+__device__ __forceinline__ int x6_rows_col(int rr, int c) { return c ^ (((rr >> 2) & 1) * 16); }
+
+template <int TM, int TN, int ABL = 0, bool C16 = false, bool ROWS = false, typename Acc>
 __device__ __forceinline__ void x6_epilogue(const GemmArgs& g, const Acc& acc, int64_t r0,
                                             int64_t c0, int64_t n0, int ks, int lane, float ia, float ib,
                                             float* __restrict__ stage) {
@@ -128,17 +150,106 @@ __device__ __forceinline__ void x6_epilogue(const GemmArgs& g, const Acc& acc, i
     // block waits for it (the main loop's staging registers are dead here: 16 float4 fit)
     // (up to 32 float4: larger tiles keep the per-row loads, their accumulators fill the VGPRs)
     constexpr bool kPre = ABL == 8 && !C16 && TN * TM * 4 <= 32;
-    float4 gpre[kPre ? TN : 1][kPre ? TM * 4 : 1];
+    // Row segments (ROWS; 16x16x32 accumulators, f32 C, the fast path only): the wave stages one
+    // 16-row block across all TN * 32 of its columns and stores each row as one contiguous segment,
+    // LPR lanes per row, RPI rows per wave instruction (64 x 128 wave tile: 512-B segments, 2 rows;
+    // 64 x 64: 256 B, 4 rows), where the column-block walk below stores 8 rows x 128 B, ldc apart.
+    // A lane keeps one column quad for the whole tile (one bias load) and walks rows only. Per
+    // element the arithmetic and its order are the column-block walk's: the same bits.
+    constexpr bool kRow = ROWS && std::is_same_v<std::remove_cv_t<std::remove_all_extents_t<Acc>>, floatx4> && !C16 &&
+                          TN <= 2 * TM && 64 % (8 * TN) == 0;   // (the block fits the [TM*32][32] stage)
+    constexpr int LPR = 8 * TN, RPI = 64 / LPR, NQ = 16 / RPI;
+    const bool rows = kRow && fast;
+    float4 gpre[kPre ? TN * TM * 4 : 1];   // [j][q] of the column-block walk, [ii][q] of the row walk
     if constexpr (kPre) {
         if (fast && g.beta != 0.f) {
+            if (rows) {
 #pragma unroll
-            for (int j = 0; j < TN; ++j)
+                for (int ii = 0; ii < 2 * TM; ++ii)
 #pragma unroll
-                for (int q = 0; q < TM * 4; ++q)
-                    gpre[j][q] = *reinterpret_cast<const float4*>(g.bsrc + (r0 + q * 8 + rq) * g.ld_bsrc + c0 + j * 32 +
-                                                                  c4 - g.bsrc_c0);
+                    for (int q = 0; q < NQ; ++q)
+                        gpre[ii * NQ + q] = *reinterpret_cast<const float4*>(
+                            g.bsrc + (r0 + ii * 16 + q * RPI + lane / LPR) * g.ld_bsrc + c0 + (lane % LPR) * 4 - g.bsrc_c0);
+            } else {
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int q = 0; q < TM * 4; ++q)
+                        gpre[j * TM * 4 + q] = *reinterpret_cast<const float4*>(
+                            g.bsrc + (r0 + q * 8 + rq) * g.ld_bsrc + c0 + j * 32 + c4 - g.bsrc_c0);
+            }
         }
     }
+    if constexpr (kRow) {
+        if (rows) {
+            const int rl = lane / LPR, cl = (lane % LPR) * 4;
+            const int64_t col = c0 + cl;
+            float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (g.bias) bv = *reinterpret_cast<const float4*>(g.bias + col);
+            const float b4[4] = {bv.x, bv.y, bv.z, bv.w};
+            const int64_t step = RPI * ldd;
+            // LD = false: nothing is loaded per row (no gathered rows; beta off, or its operand
+            // prefetched) -- the walk is instantiated for that case on its own, so its stores are not
+            // drained one by one by the vmcnt(0) a conditional load would put in front of each
+            auto walk = [&](auto ld_tag) {
+                constexpr bool LD = decltype(ld_tag)::value;
+                float* p = dst + (r0 + rl) * ldd + col;
+#pragma unroll
+                for (int ii = 0; ii < 2 * TM; ++ii) {
+                    x6_stage_write_rows<TM, TN>(stage, acc, ii, lane);
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q, p += step) {
+                        const int rr = q * RPI + rl;
+                        const int64_t row = r0 + ii * 16 + rr;
+                        const float4 sv = *reinterpret_cast<const float4*>(stage + rr * (TN * 32) + x6_rows_col(rr, cl));
+                        float e[4] = {sv.x, sv.y, sv.z, sv.w};
+                        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+                        if constexpr (LD) {
+                            if (g.ga0) {
+                                a0 = *reinterpret_cast<const float4*>(g.ga0 + g.gi0[row] * g.ldg0 + col);
+                                if (g.ga1) a1 = *reinterpret_cast<const float4*>(g.ga1 + g.gi1[row] * g.ldg1 + col);
+                            }
+                        }
+                        const float x0[4] = {a0.x, a0.y, a0.z, a0.w}, x1[4] = {a1.x, a1.y, a1.z, a1.w};
+                        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+                        if (g.beta != 0.f) {
+                            if constexpr (kPre) {
+                                beta_mask4(g, row, col, gpre[ii * NQ + q], pv);
+                            } else if constexpr (!LD) {   // (beta == 0 here)
+                            } else if constexpr (ABL == 8) {
+                                beta_src4(g, row, col, pv);
+                            } else {
+                                const float4 t = *reinterpret_cast<const float4*>(p);
+                                pv[0] = t.x; pv[1] = t.y; pv[2] = t.z; pv[3] = t.w;
+                            }
+                        }
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            float v = one_mul ? e[k] * iab : (e[k] * ia) * ib;
+                            v *= g.alpha;
+                            if (LD || kPre) {
+                                if (g.beta != 0.f) v += g.beta * pv[k];
+                            }
+                            if (g.bias) v += b4[k];
+                            if constexpr (LD) {
+                                if (g.ga0) v += x0[k];
+                                if (g.ga1) v += x1[k];
+                            }
+                            if (g.relu) v = fmaxf(v, 0.f);
+                            e[k] = v;
+                            cmax = max(cmax, __float_as_uint(v) & 0x7fffffffu);
+                        }
+                        st_nt4(p, e);
+                    }
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                }
+            };
+            if (!g.ga0 && !g.ga1 && (kPre || g.beta == 0.f)) walk(std::false_type{});
+            else walk(std::true_type{});
+        }
+    }
+    if (!rows) {   // the column-block walk: every other case
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         x6_stage_write<TM, TN>(stage, acc, j, lane);
@@ -164,7 +275,7 @@ __device__ __forceinline__ void x6_epilogue(const GemmArgs& g, const Acc& acc, i
                 float pv[4] = {0.f, 0.f, 0.f, 0.f};
                 if (g.beta != 0.f) {
                     if constexpr (kPre) {   // beta operand = masked bsrc (bgnn_gemm_f32_dropadd)
-                        beta_mask4(g, r0 + q * 8 + rq, col, gpre[j][q], pv);
+                        beta_mask4(g, r0 + q * 8 + rq, col, gpre[j * TM * 4 + q], pv);
                     } else if constexpr (ABL == 8) {
                         beta_src4(g, r0 + q * 8 + rq, col, pv);
                     } else {
@@ -265,6 +376,7 @@ __device__ __forceinline__ void x6_epilogue(const GemmArgs& g, const Acc& acc, i
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
     }
     if (g.c_amax && !split) {
         for (int o = 32; o > 0; o >>= 1) cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, o, kWave));

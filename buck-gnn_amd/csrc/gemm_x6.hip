@@ -47,6 +47,13 @@ const int kNumX6Cfgs = 6;
 // 272 -> 263 us, drop-add 321 -> 312, cfg2 step 8.74 -> 8.67 ms (profiles/r06_gemm_h3p_q.txt)
 int g_x6_bdma = 2;
 
+// knob 17 (BGNN_TUNE_GEMM_CSTORE): the store shape of x6_epilogue's interior path in the f16x3 NT
+// kernels on 16x16x32 accumulators (gemm_x6.h): 0 = 32-column blocks, 1 = whole row segments of the
+// wave tile (their own instantiations: gemm_x6_ntr.hip, gemm_h3p.hip). Default 1: bit-identical, forward
+// 268 -> 251 us, folded forward 138 -> 124, dgrad 251 -> 243, cfg2 step 7.34-7.39 -> 7.22-7.27 ms
+// (profiles/r09_gemm_ab_rowseg.txt, r09_yardstick.txt)
+int g_x6_rowseg = 1;
+
 void launch_x6(int prec, int ta, int tb, int cfg, int abl, dim3 grid, hipStream_t s, const GemmArgs& g) {
     if (prec == 2 && g.st != 0) launch_x6_bf16_storage(ta, tb, cfg, g.st, grid, s, g);
     else if (prec == 2) launch_x6_prec2(ta, tb, cfg, grid, s, g);

@@ -47,6 +47,7 @@ __device__ __forceinline__ void x6_barrier_lds() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
+extern int g_x6_rowseg;   // knob 17: 1 = the row-segment C stores (PPV bit 5; gemm_x6.hip)
 extern int g_x6_bdma;   // 1: the pre-split f16x3 GEMMs stage B by LDS-DMA, 2-4: k_gemm_h3p (gemm_x6.hip)
 struct GemmArgs;
 bool h3p_ok(int cfg, const GemmArgs& g);                                // gemm_h3p.hip
@@ -367,6 +368,9 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_x6(GemmArgs g) {
     // that a SIMD's two waves do not leave the matrix pipe for their staging together (the guide's
     // stagger; the pre-split 256 x 256 forward)
     constexpr bool kSTG = (PPV & 16) != 0;
+    // PPV bit 5 (32): interior tiles store C in whole row segments of the wave tile (x6_epilogue<ROWS>;
+    // 16x16x32 accumulators with an f32 C, else no effect); the same bits
+    constexpr bool kRS = (PPV & 32) != 0;
     static_assert(!kDMA || (kWB && PREC == 1 && 64 * WM * WN == 512), "B by LDS-DMA: pre-split f16x3, 8 waves");
     // f16x3 main loops run 16x16x32 MFMAs (four per 32x32 block, one per 32-deep slice; round 5):
     // the same cycles per FLOP as 32x32x16, but the chip holds a higher clock under them (guide
@@ -726,18 +730,19 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_x6(GemmArgs g) {
         GemmArgs ge = g;
         ge.beta = 0.f;
         if constexpr (kM16)
-            x6_epilogue<TM, TN, ABL, C16>(ge, acc4, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
+            x6_epilogue<TM, TN, ABL, C16, kRS>(ge, acc4, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
         else
-            x6_epilogue<TM, TN, ABL, C16>(ge, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
+            x6_epilogue<TM, TN, ABL, C16, kRS>(ge, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
         return;
     }
     if constexpr (kM16)
-        x6_epilogue<TM, TN, ABL, C16>(g, acc4, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
+        x6_epilogue<TM, TN, ABL, C16, kRS>(g, acc4, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
     else
-        x6_epilogue<TM, TN, ABL, C16>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
+        x6_epilogue<TM, TN, ABL, C16, kRS>(g, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), n0, ks, lane, ia, ib, stage);
 }
 
-template <int PREC, int TA, int TB, int ABL>
+// RS = 32: the row-segment instantiations (PPV bit 5) of the 8-wave tiles
+template <int PREC, int TA, int TB, int ABL, int RS = 0>
 inline void launch_x6_a(int cfg, dim3 grid, hipStream_t s, const GemmArgs& g) {
     if constexpr (PREC == 1 && TA == 0 && TB == 1) {
         if (g.wb && g_x6_bdma >= 2 && h3p_ok(cfg, g)) {   // the pipelined kernels (gemm_h3p.hip)
@@ -747,45 +752,46 @@ inline void launch_x6_a(int cfg, dim3 grid, hipStream_t s, const GemmArgs& g) {
 #ifdef BGNN_H3P_ABLATION
         if (g.wb && g_x6_bdma == 1) {   // the same tiles with B staged by LDS-DMA (measurement build only)
             switch (cfg) {
-                case 1: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 128, 4, 2, ABL, 12>), grid, dim3(512), 0, s, g); return;
-                case 2: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 256, 2, 4, ABL, 12>), grid, dim3(512), 0, s, g); return;
-                case 3: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 2, 4, ABL, 12>), grid, dim3(512), 0, s, g); return;
-                default: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 4, 2, ABL, 12>), grid, dim3(512), 0, s, g); return;
+                case 1: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 128, 4, 2, ABL, 12 | RS>), grid, dim3(512), 0, s, g); return;
+                case 2: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 256, 2, 4, ABL, 12 | RS>), grid, dim3(512), 0, s, g); return;
+                case 3: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 2, 4, ABL, 12 | RS>), grid, dim3(512), 0, s, g); return;
+                default: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 4, 2, ABL, 12 | RS>), grid, dim3(512), 0, s, g); return;
             }
         }
 #endif
         if (g.wb) {   // pre-split B image (bgnn_gemm_f32_w): tiles with BN = the image's column tile
             switch (cfg) {
-                case 1: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 128, 4, 2, ABL, 4>), grid, dim3(512), 0, s, g); return;
-                case 2: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 256, 2, 4, ABL, 4>), grid, dim3(512), 0, s, g); return;
-                case 3: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 2, 4, ABL, 4>), grid, dim3(512), 0, s, g); return;
+                case 1: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 128, 4, 2, ABL, 4 | RS>), grid, dim3(512), 0, s, g); return;
+                case 2: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 256, 2, 4, ABL, 4 | RS>), grid, dim3(512), 0, s, g); return;
+                case 3: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 2, 4, ABL, 4 | RS>), grid, dim3(512), 0, s, g); return;
                 // (the forward's 256 x 256 tile with the staggered staging, PPV 16: 290.5 -> 283.5 us,
                 // bit-identical, profiles/r06_gemm_fwd_stagger_aa.txt)
-                default: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 4, 2, ABL, 20>), grid, dim3(512), 0, s, g); return;
+                default: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 4, 2, ABL, 20 | RS>), grid, dim3(512), 0, s, g); return;
             }
         }
     }
     // 256x256 tiles (cfg 3, 4): f16x3 and bf16 (one or two pieces fit the LDS). The tile here must
     // be the plan's tile (bgnn_gemm_f32_scaled sizes the grid from it).
     if constexpr (PREC >= 1) {
-        if (cfg == 3) { hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 2, 4, ABL>), grid, dim3(512), 0, s, g); return; }
+        if (cfg == 3) { hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 2, 4, ABL, RS>), grid, dim3(512), 0, s, g); return; }
         // (round 6: the staggered staging on the weight gradient's 256 x 256 tile measured 259.9 ->
         // 260.7 us, profiles/r06_gemm_wgrad_stagger_ac.txt; not used)
-        if (cfg == 4) { hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 4, 2, ABL>), grid, dim3(512), 0, s, g); return; }
+        if (cfg == 4) { hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 256, 4, 2, ABL, RS>), grid, dim3(512), 0, s, g); return; }
     }
     if constexpr (PREC == 1 && TA == 0 && TB == 1) {
-        if (cfg == 5) { hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 128, 2, 4, ABL>), grid, dim3(512), 0, s, g); return; }
+        if (cfg == 5) { hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 128, 2, 4, ABL, RS>), grid, dim3(512), 0, s, g); return; }
     }
     switch (cfg) {
         case 0: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 128, 2, 2, ABL>), grid, dim3(256), 0, s, g); break;
-        case 2: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 256, 2, 4, ABL>), grid, dim3(512), 0, s, g); break;
-        default: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 128, 4, 2, ABL>), grid, dim3(512), 0, s, g); break;
+        case 2: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 128, 256, 2, 4, ABL, RS>), grid, dim3(512), 0, s, g); break;
+        default: hipLaunchKernelGGL((k_gemm_x6<PREC, TA, TB, 256, 128, 4, 2, ABL, RS>), grid, dim3(512), 0, s, g); break;
     }
 }
 
 
 // per-family launchers (one translation unit each)
 void launch_x6_nt_main(int cfg, int abl, dim3 grid, hipStream_t s, const GemmArgs& g);    // gemm_x6_nt.hip
+void launch_x6_nt_rows(int cfg, int abl, dim3 grid, hipStream_t s, const GemmArgs& g);    // gemm_x6_ntr.hip
 void launch_x6_h3_other(int ta, int tb, int cfg, dim3 grid, hipStream_t s, const GemmArgs& g);  // _other
 void launch_x6_prec2(int ta, int tb, int cfg, dim3 grid, hipStream_t s, const GemmArgs& g);        // _b16s
 void launch_x6_bf16_storage(int ta, int tb, int cfg, int st, dim3 grid, hipStream_t s, const GemmArgs& g);

@@ -6,6 +6,7 @@
 namespace bgnn {
 
 void launch_x6_nt_main(int cfg, int abl, dim3 grid, hipStream_t s, const GemmArgs& g) {
+    if (g_x6_rowseg) return launch_x6_nt_rows(cfg, abl, grid, s, g);   // (knob 17; gemm_x6_ntr.hip)
     if (abl == 8) launch_x6_a<1, 0, 1, 8>(cfg, grid, s, g);
     else launch_x6_a<1, 0, 1, 0>(cfg, grid, s, g);
 }

@@ -7,6 +7,7 @@
 namespace bgnn {
 
 extern int g_x6_bdma;   // gemm_x6.hip
+extern int g_x6_rowseg;
 extern int g_h3p_nsb;   // gemm_h3p.hip
 #ifdef BGNN_H3P_ABLATION
 extern int g_h3p_abl;
@@ -27,6 +28,7 @@ extern "C" int32_t bgnn_get_tuning(int32_t knob) {
         case BGNN_TUNE_GROUP_BLOCKS: return g_seg.grp_blocks;
         case BGNN_TUNE_ROWS_REV: return rows_rev();
         case BGNN_TUNE_GEMM_BDMA: return g_x6_bdma == 2 && g_h3p_nsb == 4 ? 3 : g_x6_bdma;
+        case BGNN_TUNE_GEMM_CSTORE: return g_x6_rowseg;
         default: return -1;
     }
 }
@@ -70,6 +72,11 @@ extern "C" int bgnn_set_tuning(int32_t knob, int32_t value) {
 #endif
             g_x6_bdma = value == 3 ? 2 : value;
             g_h3p_nsb = value == 3 ? 4 : 3;
+            return BGNN_OK;
+        case BGNN_TUNE_GEMM_CSTORE:
+            BGNN_REQUIRE(value == 0 || value == 1, "set_tuning: gemm C store shape must be 0 (column blocks) or 1 "
+                                                   "(row segments)");
+            g_x6_rowseg = value;
             return BGNN_OK;
         case BGNN_TUNE_GEMM_MODE:
             BGNN_REQUIRE(value == 0 || value == 2, "set_tuning: gemm mode must be 0 (f32 MFMA) or 2 (f16x3)");

@@ -92,6 +92,11 @@ const char* bgnn_last_error_string(void);
                                     kernel (gemm_h3p.hip: B by LDS-DMA into 3 / 4 slots, the next
                                     slice's fragments read under the current MFMAs). Default 3.
                                     Bit-identical for every setting                           */
+#define BGNN_TUNE_GEMM_CSTORE 17 /* how interior tiles of the 16-bit-MFMA GEMMs with 16x16x32
+                                    accumulators and an f32 C store it: 0 = 32-column blocks, 8
+                                    rows x 128 B per wave instruction; 1 = whole row segments of
+                                    the wave tile (64 x 128 waves: 2 rows x 512 B, 64 x 64 waves:
+                                    4 rows x 256 B). Default 1. Bit-identical for either setting */
 /* Heavy-row timing (measurement only): while enabled, every aggregation launch with super-node
  * chunks records a HIP event pair around its chunk + combine kernels. Enabling resets the record.
  * read: which = 0 the forward aggregations (bgnn_sage_fwd, bgnn_spmm_fwd), 1 the transpose

@@ -12,7 +12,10 @@ automatic plan); "w" the pre-split weight path (bgnn_gemm_wsplit + bgnn_gemm_f32
 with the drop-add epilogue (src = an [M, N] gradient, p = 0.1: the skip layers' dgrad), "n" that epilogue
 with p = 0 (no dropout mask); "w.C" /
 "d.C" on tile config C; "W", "D" (and "W.C", "D.C") the same with B staged by LDS-DMA (knob 16 = 1); a suffix "@V" sets
-knob 16 (BGNN_TUNE_GEMM_BDMA) to V for that variant ("w@2": the pipelined kernel gemm_h3p.hip). (Round 6 measured the main-loop variants "wP" of the then knob 14 here,
+knob 16 (BGNN_TUNE_GEMM_BDMA) to V for that variant ("w@2": the pipelined kernel gemm_h3p.hip); a final "+r" / "+c"
+sets knob 17 (BGNN_TUNE_GEMM_CSTORE) to the row-segment / column-block C stores ("w+r", "d@3+c"; neither: the
+library's default); a trailing "#n" only tells two timings of the same variant apart ("w+c,w+c#2,w+r": the spread
+between the two medians of one variant is the noise floor of that process). (Round 6 measured the main-loop variants "wP" of the then knob 14 here,
 profiles/r06_gemm_ab_b.txt.)
 """
 import argparse
@@ -31,7 +34,8 @@ SHAPES = {"wgrad": (1024, 512, 80656), "fwd": (80656, 1024, 512), "dgrad": (8065
 
 
 def parse(vs):
-    """-> (kind, knob-16 value, tile cfg)"""
+    """-> (kind, knob-16 value, tile cfg); the "+r" / "+c" suffix is parse_cstore's"""
+    vs = vs.partition("#")[0].partition("+")[0]
     vs, _, kv = vs.partition("@")
     kind = vs[0]
     if kind in "WD":   # the w / d variants with B staged by LDS-DMA (knob 16 = 1)
@@ -45,6 +49,12 @@ def parse(vs):
     return kind, knob, int(cfg) if cfg else -1
 
 
+def parse_cstore(vs, default):
+    """knob-17 value of a variant"""
+    sfx = vs.partition("#")[0].partition("+")[2]
+    return {"": default, "r": 1, "c": 0}[sfx]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -56,6 +66,7 @@ def main():
     dev = torch.device("cuda", 0)
     flush = None if args.no_flush else torch.empty(1 << 28, device=dev)
     variants = args.variants.split(",")
+    cstore0 = _lib.query("bgnn_get_tuning", 17)   # (-1: a library from before the knob; "+r" / "+c" then fail)
     for name in args.shapes.split(","):
         M, N, K = SHAPES[name]
         torch.manual_seed(0)
@@ -87,6 +98,8 @@ def main():
                 kind, pp, cfg = parse(vs)
                 _lib.call("bgnn_gemm_set_cfg", cfg)
                 _lib.call("bgnn_set_tuning", 16, pp)
+                if parse_cstore(vs, cstore0) >= 0:
+                    _lib.call("bgnn_set_tuning", 17, parse_cstore(vs, cstore0))
                 if flush is not None:
                     flush.fill_(float(i))
                 out = outs[vs]
@@ -107,6 +120,8 @@ def main():
                     times[vs].append((e0, e1))
         _lib.call("bgnn_gemm_set_cfg", -1)
         _lib.call("bgnn_set_tuning", 16, 3)
+        if cstore0 >= 0:
+            _lib.call("bgnn_set_tuning", 17, cstore0)
         torch.cuda.synchronize()
         ref = {}
         for vs in variants:
@@ -116,7 +131,7 @@ def main():
             r = ref.setdefault(kind, outs[vs])
             same = "ref" if r is outs[vs] else ("bit-identical" if torch.equal(outs[vs], r) else
                                                 f"DIFFERS max {(outs[vs] - r).abs().max().item():.3g}")
-            print(f"{name:9s} {M}x{N}x{K} {vs:>6s}: median {med:7.1f} us  min {us[0]:7.1f}  "
+            print(f"{name:9s} {M}x{N}x{K} {vs:>10s}: median {med:7.1f} us  min {us[0]:7.1f}  "
                   f"{2 * M * N * K / med / 1e6:6.1f} TF  {same}", flush=True)
 
 
