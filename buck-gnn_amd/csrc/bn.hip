@@ -178,6 +178,9 @@ extern "C" int bgnn_bn_bwd_dx(const float* g, const float* x, const float* mean,
     BGNN_REQUIRE(bn_shape_ok(C), "bn_bwd_dx: C=%d unsupported", C);
     BGNN_REQUIRE(g && x && mean && invstd && sums && dx && aligned16(g) && aligned16(x) && aligned16(dx),
                  "bn_bwd_dx: 16-byte aligned g / x / dx required");
+    // the kernel reads the per-column vectors as float4 too
+    BGNN_REQUIRE(aligned16(mean) && aligned16(invstd) && aligned16(sums) && aligned16(gamma),
+                 "bn_bwd_dx: 16-byte aligned mean / invstd / gamma / sums required");
     const int64_t n4 = n_rows * C / 4;
     if (n4 == 0) return BGNN_OK;
     hipLaunchKernelGGL(k_bn_rows<1>, dim3(rows_blocks(n4)), dim3(256), 0, as_stream(stream),

@@ -575,7 +575,9 @@ extern "C" int bgnn_mlp2_bwd(const float* x, int64_t N, int32_t F, int32_t D1, i
         return BGNN_OK;
     }
     BGNN_REQUIRE(x && W1 && W2 && h && dh, "mlp2_bwd: null pointer");
-    BGNN_REQUIRE(ws && ws_bytes >= bgnn_mlp2_bwd_ws_bytes(N), "mlp2_bwd: workspace too small");
+    BGNN_REQUIRE(aligned16(h) && aligned16(dh), "mlp2_bwd: h and dh must be 16-byte aligned");
+    BGNN_REQUIRE(ws && aligned16(ws) && ws_bytes >= bgnn_mlp2_bwd_ws_bytes(N),
+                 "mlp2_bwd: workspace too small or not 16-byte aligned");
     const int blocks = mlp_blocks(N);
     float* part = static_cast<float*>(ws);
     const size_t dyn = sizeof(float) * kT * ((kD2 + 4) + (kD1 + 4));

@@ -891,6 +891,8 @@ int bgnn_filter_edges(const int64_t* edge_index, int64_t num_edges, const int32_
  * bgnn_mlp2_fwd folds max|h| into *h_amax (f32 bits, atomic max; NULL = off).
  * bgnn_mlp2_bwd: given dh = dL/dh, the weight / bias gradients of both layers (written, not
  * accumulated), deterministic (per-workgroup partials summed in order); x gets no gradient.
+ * h (both entries), dh and ws (bgnn_mlp2_bwd_ws_bytes(N) bytes) 16-byte aligned; b1 / b2 may be
+ * NULL (zeros). N = 0: no launch (the backward zero-fills the four gradients).
  * bgnn_mlp2_supported: whether (F, D1, D2) is built (only 16 x 64 x 128).
  * ---------------------------------------------------------------------- */
 int bgnn_mlp2_supported(int32_t F, int32_t D1, int32_t D2);
@@ -923,7 +925,8 @@ int bgnn_add_dropout(const float* a, const float* b, int64_t n, float p, uint64_
  *   bgnn_bn_bwd_stats: partials of sum g, sum g * (x - mean) * invstd (finished by
  *                      bgnn_reduce_partials into sums[2, C] = dbeta, dgamma)
  *   bgnn_bn_bwd_dx:    train-mode input gradient gamma invstd / N (N g - sums[0] - xhat sums[1])
- *                      (gamma may be NULL: affine=False)
+ *                      (gamma may be NULL: affine=False; mean, invstd, gamma and sums [2, C] are
+ *                      read in 16-byte vectors like g, x and dx: BGNN_E_ARG if one is unaligned)
  * ---------------------------------------------------------------------- */
 int32_t bgnn_bn_slots(int64_t n_rows, int32_t C);
 int bgnn_bn_stats(const float* x, int64_t n_rows, int32_t C, float* partial, void* stream);

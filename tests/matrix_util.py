@@ -1,6 +1,6 @@
 """The window machinery of the GPU conformance matrices (tests/test_gpu_sage_rows_matrix.py,
-tests/test_gpu_spmm_matrix.py): outputs as NaN-filled windows inside guarded allocations, inputs
-with NaN after their last row, the comparison against an fp64 reference under a per-element bound
+tests/test_gpu_spmm_matrix.py, tests/test_gpu_dense_matrix.py): outputs as NaN-filled windows inside guarded allocations,
+inputs with NaN after their last row, the comparison against an fp64 reference under a per-element bound
 with the largest err / bound kept per section, and the amax check."""
 import torch
 
@@ -38,6 +38,34 @@ class Out:
         bad = (g != PATTERN).nonzero().flatten()
         assert bad.numel() == 0, (f"{label}: {bad.numel()} guard elements outside the {self.rows} x {self.cols} "
                                   f"window (ld {self.ld}) overwritten; first at flat offset {int(bad[0])}")
+
+
+class OutB16:
+    """n bf16 output elements starting as NaN (0x7FC0), 64 guard elements of PATTERN16 on either side (the
+    window starts on a 16-byte boundary)"""
+    PATTERN16 = 0x4B1D    # (as bf16: 1.03e7, finite)
+    GUARD = 64
+
+    def __init__(self, dev, n):
+        self.n = n
+        self.buf = torch.full((n + 2 * self.GUARD,), self.PATTERN16, dtype=torch.int16, device=dev)
+        self.buf[self.GUARD:self.GUARD + n] = 0x7FC0
+        self.ptr = self.buf.data_ptr() + 2 * self.GUARD
+
+    def read(self):
+        return self.buf[self.GUARD:self.GUARD + self.n].cpu().view(torch.bfloat16)
+
+    def guard(self, label):
+        g = torch.cat([self.buf[:self.GUARD], self.buf[self.GUARD + self.n:]])
+        bad = (g != self.PATTERN16).nonzero().flatten()
+        assert bad.numel() == 0, f"{label}: {bad.numel()} bf16 guard elements around the {self.n}-element window overwritten"
+
+
+def inp16(dev, t, pad=2):
+    """a bf16 [rows, cols] input on the device with NaN in `pad` rows after its last"""
+    buf = torch.full((t.size(0) + pad, t.size(1)), NAN, dtype=torch.bfloat16)
+    buf[:t.size(0)] = t
+    return buf.to(dev)
 
 
 def scalar(dev, v):

@@ -82,6 +82,31 @@ def test_kernel_bits_fp64_strided_deterministic(dev, D0, C):
         assert torch.equal(_run16(x, W1, b1, W2, b2), y), (D0, C, N)
 
 
+@pytest.mark.parametrize("nb1,nb2", [(1, 0), (0, 1), (1, 1)])
+def test_kernel_null_biases(dev, nb1, nb2):
+    """b1 / b2 = NULL (zeros, as the header allows): the bits of bgnn_head2_fwd with the same NULLs, and
+    of both entries given zero vectors"""
+    D0, C, N = 128, 5, _rows()[3]
+    x, W1, b1, W2, b2, _ = _case(D0, C, N)
+    x, W1, b1, W2, b2 = (t.to(dev) for t in (x, W1, b1, W2, b2))
+    z1, z2 = torch.zeros_like(b1), torch.zeros_like(b2)
+
+    def call(name, xx, head, p1, p2):
+        y = torch.full((N, C), float("nan"), device=dev)
+        _lib.call(name, xx.data_ptr(), *head, N, D0, 64, C, W1.data_ptr(), p1, W2.data_ptr(), p2, y.data_ptr(), _stream())
+        return y
+
+    p1, p2 = (None if nb1 else b1.data_ptr()), (None if nb2 else b2.data_ptr())
+    q1, q2 = (z1 if nb1 else b1).data_ptr(), (z2 if nb2 else b2).data_ptr()
+    y = call("bgnn_head2_fwd_bf16", x, (x.stride(0),), p1, p2)
+    assert bool(torch.isfinite(y).all())
+    assert torch.equal(y, call("bgnn_head2_fwd", x.float(), (), p1, p2))
+    assert torch.equal(y, call("bgnn_head2_fwd_bf16", x, (x.stride(0),), q1, q2))
+    b1d, b2d = (z1 if nb1 else b1).double().cpu(), (z2 if nb2 else b2).double().cpu()
+    y64 = torch.relu(x.double().cpu() @ W1.double().cpu().t() + b1d) @ W2.double().cpu().t() + b2d
+    torch.testing.assert_close(y.double().cpu(), y64, rtol=1e-5, atol=1e-5)
+
+
 def _h512_decoder(dev, C=3):
     torch.manual_seed(5)
     seq = torch.nn.Sequential(torch.nn.Linear(512, 128), torch.nn.ReLU(), torch.nn.Linear(128, 64), torch.nn.ReLU(),
