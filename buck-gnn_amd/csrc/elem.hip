@@ -269,7 +269,8 @@ extern "C" int bgnn_rel_error_loss(const float* pred, const float* y, int64_t n,
 
 extern "C" int bgnn_segment_sum_bf16(const int32_t* rowptr, const int32_t* col, int64_t n_rows, const void* x,
                                      int64_t ldx, int32_t H, int32_t mean, float* out, int64_t ldo, void* stream) {
-    BGNN_REQUIRE(rowptr && (n_rows == 0 || (col && x && out)), "segment_sum_bf16: null pointer");
+    BGNN_REQUIRE(n_rows >= 0 && rowptr && (n_rows == 0 || (col && x && out)),
+                 "segment_sum_bf16: null pointer or n_rows < 0");
     BGNN_REQUIRE(H > 0 && H <= 512 && H % 8 == 0 && ldx % 8 == 0 && ldx >= H && ldo >= H && ldo % 4 == 0,
                  "segment_sum_bf16: H must be a multiple of 8 up to 512, rows 16-B aligned");
     BGNN_REQUIRE(aligned16(x) && aligned16(out), "segment_sum_bf16: 16-byte aligned x / out required");
@@ -284,7 +285,8 @@ extern "C" int bgnn_segment_sum_bf16(const int32_t* rowptr, const int32_t* col, 
 
 extern "C" int bgnn_segment_bcast_bf16(const int32_t* rowptr, const int32_t* col, int64_t n_rows, const float* g,
                                        int64_t ldg, int32_t H, int32_t mean, void* out, int64_t ldo, void* stream) {
-    BGNN_REQUIRE(rowptr && (n_rows == 0 || (col && g && out)), "segment_bcast_bf16: null pointer");
+    BGNN_REQUIRE(n_rows >= 0 && rowptr && (n_rows == 0 || (col && g && out)),
+                 "segment_bcast_bf16: null pointer or n_rows < 0");
     BGNN_REQUIRE(H > 0 && H <= 512 && H % 8 == 0 && ldg % 4 == 0 && ldg >= H && ldo >= H && ldo % 8 == 0,
                  "segment_bcast_bf16: H must be a multiple of 8 up to 512, rows 16-B aligned");
     BGNN_REQUIRE(aligned16(g) && aligned16(out), "segment_bcast_bf16: 16-byte aligned g / out required");

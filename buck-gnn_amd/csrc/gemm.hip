@@ -874,6 +874,9 @@ extern "C" int bgnn_gemm_bf16(int32_t ta, int32_t tb, int64_t M, int64_t N, int6
     const bool tn_ok = ta == 1 && tb == 0 && storage <= 3;
     BGNN_REQUIRE(storage == 0 || nt_ok || tn_ok, "gemm_bf16: storage %d with ta=%d tb=%d is not built", storage, ta,
                  tb);
+    // (M == 0 or N == 0 returns below without a launch; K == 0 reads neither operand)
+    BGNN_REQUIRE(M <= 0 || N <= 0 || (C != nullptr && (K <= 0 || (A != nullptr && B != nullptr))),
+                 "gemm_bf16: null A / B / C");
     return gemm_scaled_impl(ta, tb, M, N, K, alpha, static_cast<const float*>(A), lda, 0, 0,
                             static_cast<const float*>(B), ldb, beta, static_cast<float*>(C), ldc, 0, 0, bias, relu,
                             nullptr, nullptr, nullptr, 1, ws, ws_bytes, stream, BetaSrc{nullptr, 0, 0, 0.f}, storage);
@@ -889,6 +892,8 @@ extern "C" int bgnn_gemm_gather_add_bf16(int64_t M, int64_t N, int64_t K, const 
                                          size_t ws_bytes, void* stream) {
     BGNN_REQUIRE(storage >= 0 && storage < 8 && storage != 2 && storage != 6,
                  "gemm_gather_add_bf16: storage must be one of 0, 1, 3, 4, 5, 7");
+    BGNN_REQUIRE(M <= 0 || N <= 0 || (C != nullptr && (K <= 0 || (A != nullptr && B != nullptr))),
+                 "gemm_gather_add_bf16: null A / B / C");
     return gather_add_impl(0, 1, M, N, K, static_cast<const float*>(A), lda, static_cast<const float*>(B), ldb,
                            static_cast<float*>(C), ldc, bias,
                            relu, add0, idx0, ld0, add1, idx1, ld1, 1, ws, ws_bytes, stream, storage);

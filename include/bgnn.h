@@ -601,14 +601,18 @@ int bgnn_l2norm_bwd(const float* g, const float* o, const float* nrm, int64_t n_
  *   bf16 kernel (ABI 6, gemm_b16.hip), bit-identical to the register-staged one.
  * bgnn_gemm_gather_add_bf16: bgnn_gemm_gather_add (C = A B^T, bf16 operands) with storage
  *   0/1/3/4/5/7 (B bf16 = the weight rounded once by the caller; ABI 6 takes B as const void*).
+ *   Both: BGNN_E_ARG, before anything is launched, when M, N > 0 and C is NULL, or K > 0 too
+ *   and A or B is NULL (M == 0 or N == 0: BGNN_OK, nothing launched; K == 0 reads no operand
+ *   and stores act(bias (+ the gathered rows))).
  * bgnn_gemm_b16_variant (ABI 6, measurement): -1 = the bf16-stored NT products on the
- *   register-staged kernel instead; 0 = default (variant 11: one 256x256 tile per workgroup,
- *   whole-line bf16 C stores, a gathered epilogue's row indices staged in LDS); 1-14 = fixed
- *   forms (A/B; 13 = variant 11 reading the gather indices from global memory per row, 14 =
- *   variant 11 loading each 32-row block's first gathered rows before its staging).
+ *   register-staged kernel instead; 0 = default (the LDS-DMA kernel: one 256x256 tile per
+ *   workgroup, whole-line bf16 C stores, a gathered epilogue's row indices staged in LDS).
+ *   Every other value is BGNN_E_ARG (ABI 12 removed the fixed forms 1-14).
  * bgnn_add_dropout_bf16: bgnn_add_dropout over bf16 (same mask; f32 sum, one rounding).
- * bgnn_segment_sum_bf16: out[r] = sum (mean: / max(deg, 1)) of the bf16 rows x[col[p]], p in
- *   [rowptr[r], rowptr[r+1]), in CSR order, f32 result (H % 8 == 0, H <= 512). */
+ * bgnn_segment_sum_bf16: out[r] = sum of the bf16 rows x[col[p]], p in [rowptr[r], rowptr[r+1]),
+ *   in CSR order, f32 accumulation and result (H % 8 == 0, H <= 512); mean: the f32 sum times
+ *   the correctly rounded f32 reciprocal of max(deg, 1) -- a product, two roundings, not a
+ *   division (it differs from sum / deg by at most one more rounding). */
 int bgnn_gemm_bf16(int32_t trans_a, int32_t trans_b, int64_t M, int64_t N, int64_t K, float alpha,
                    const void* A, int64_t lda, const void* B, int64_t ldb, float beta, void* C, int64_t ldc,
                    const float* bias, int32_t relu, int32_t storage, void* ws, size_t ws_bytes, void* stream);
@@ -622,7 +626,12 @@ int bgnn_add_dropout_bf16(const void* a, const void* b, int64_t n, float p, uint
                           void* stream);
 /* ABI 8: out = a + drop(b) over bf16 (n a multiple of 8, 16-B aligned; out may alias a): b masked
  * with bgnn_add_dropout_bf16's mask for (p, seed) -- EA_GNN's edge-activation gradient that sums
- * an edge Linear's input gradient (a) and the skip + dropout's gradient (b) in one pass. */
+ * an edge Linear's input gradient (a) and the skip + dropout's gradient (b) in one pass.
+ * Per element out = bf16(a + w * f32(1 / (1 - p))) for a kept w = b, bf16(a) = a for a dropped
+ * one (and for b = 0, and for p = 0: exact). Whether the product and the sum round separately or
+ * as one fused multiply-add is the compiler's choice, so a kept element is pinned only to
+ * |out - (a + w ik)| <= 2^-8 |a + w ik| + 2^-23 (|a| + |w ik|), not bit for bit; the kept set
+ * and the untouched elements are exact (tests/test_gpu_gemm_b16_matrix.py, section E). */
 int bgnn_add_dropped_bf16(const void* a, const void* b, int64_t n, float p, uint64_t seed, void* out,
                           void* stream);
 /* ABI 11: C = round(round(A B^T) + drop(src)), A [M, K], B [N, K], C and src [M, N] all bf16,

@@ -1,5 +1,5 @@
 """The window machinery of the GPU conformance matrices (tests/test_gpu_sage_rows_matrix.py,
-tests/test_gpu_spmm_matrix.py, tests/test_gpu_dense_matrix.py): outputs as NaN-filled windows inside guarded allocations,
+tests/test_gpu_spmm_matrix.py, tests/test_gpu_dense_matrix.py, tests/test_gpu_gemm_b16_matrix.py): outputs as NaN-filled windows inside guarded allocations,
 inputs with NaN after their last row, the comparison against an fp64 reference under a per-element bound
 with the largest err / bound kept per section, and the amax check."""
 import torch
@@ -96,6 +96,55 @@ class In:
         host[4 + lead:4 + lead + rows * ld].view(rows, ld)[:, :cols] = t
         self.buf = host.to(dev)
         self.ptr = self.buf.data_ptr() + 4 * (4 + lead)
+
+
+class Win:
+    """A rows x cols output window of f32 or bf16 elements (row stride ld, its first element `shift` elements
+    past a 16-byte boundary) inside an allocation that holds the 32-bit PATTERN: at least two guard rows
+    above and below and the ld padding; the window starts as NaN or as `init`. The guard is compared in
+    the element's own width (a bf16 window: as 16-bit words, 0x5EED / 0x4B1D alternating)."""
+
+    def __init__(self, dev, rows, cols, ld, dtype=torch.float32, shift=0, init=None):
+        self.rows, self.cols, self.ld, self.dtype = rows, cols, ld, dtype
+        bf = dtype == torch.bfloat16
+        self.ity = torch.int16 if bf else torch.int32
+        off = (2 * ld + 7) // 8 * 8 + 8 + shift
+        n = (off + (rows + 2) * ld + 16 + 1) // 2 * 2
+        words = torch.full((n // 2 if bf else n,), PATTERN, dtype=torch.int32, device=dev)
+        self.raw = words.view(self.ity)
+        self.expect = self.raw.clone()
+        self.idx = (off + torch.arange(rows).view(rows, 1) * ld + torch.arange(cols).view(1, cols)).to(dev)
+        if init is None:
+            self.raw[self.idx] = 0x7FC0 if bf else 0x7FC00000
+        else:
+            self.raw[self.idx] = init.to(dtype).contiguous().view(self.ity).view(rows, cols).to(dev)
+        self.ptr = words.data_ptr() + (2 if bf else 4) * off
+
+    def read(self):
+        return self.raw[self.idx].cpu().view(self.dtype)
+
+    def guard(self, label):
+        g = self.raw.clone()
+        g[self.idx] = self.expect[self.idx]
+        bad = (g != self.expect).nonzero().flatten()
+        assert bad.numel() == 0, (f"{label}: {bad.numel()} guard elements outside the {self.rows} x {self.cols} "
+                                  f"{self.dtype} window (ld {self.ld}) overwritten; first at flat offset {int(bad[0])}, "
+                                  f"window at {int(self.idx[0, 0]) if self.idx.numel() else 0}")
+
+
+class Buf:
+    """An f32 or bf16 [rows, cols] input with row stride ld >= cols, its first element `shift` elements past
+    a 16-byte boundary: NaN in the ld padding, before the first row and in two rows after the last -- a
+    read outside the rows' columns poisons."""
+
+    def __init__(self, dev, t, ld=None, dtype=torch.float32, shift=0):
+        rows, cols = t.shape
+        self.ld = ld = cols if ld is None else ld
+        assert ld >= cols
+        host = torch.full((8 + shift + (rows + 2) * ld + 8,), NAN, dtype=dtype)
+        host[8 + shift:8 + shift + rows * ld].view(rows, ld)[:, :cols] = t.to(dtype)
+        self.buf = host.to(dev)
+        self.ptr = self.buf.data_ptr() + host.element_size() * (8 + shift)
 
 
 def ptr(t):
