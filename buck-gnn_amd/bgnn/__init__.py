@@ -19,7 +19,8 @@ from .dataset import load_dataset_cache
 from .inference import evaluate, evaluate_nodes
 from .train import ColumnScaler, EigenvalueScaler, GradAllReduce, RelativeErrorLoss, mape_error, train_step
 from .fused import node_head, node_head_bf16
-from . import losses
+from . import losses, pool
+from .pool import gather_scale_bf16, sag_pool_bf16, sag_score_bf16
 from .losses import (GraphMAELoss, GraphMaxComponentRelativeError, GraphMixedError, GraphMSELoss,
                      GraphRelativeError, ScaledGraphMAELoss, ScaledGraphMSELoss, ScaledGraphRELoss, StressErrorMeter,
                      get_loss_function, graph_metrics, stress_errors)
@@ -33,7 +34,8 @@ __all__ = [
     "save_checkpoint", "load_dataset_cache", "evaluate", "losses", "GraphMAELoss", "GraphMaxComponentRelativeError", "GraphMixedError",
     "GraphMSELoss", "GraphRelativeError", "stress_errors", "ColumnScaler", "node_head", "node_head_bf16",
     "evaluate_nodes", "StressErrorMeter", "graph_metrics", "ScaledGraphMAELoss", "ScaledGraphMSELoss",
-    "ScaledGraphRELoss", "get_loss_function", "readout_for", "register_readout",
+    "ScaledGraphRELoss", "get_loss_function", "readout_for", "register_readout", "sag_score_bf16",
+    "gather_scale_bf16", "sag_pool_bf16",
 ]
 
 

@@ -157,6 +157,9 @@ SIGNATURES = {
     "bgnn_topk_select": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "bgnn_gather_scale": (c_i32, [c_p, c_i64, c_i32, c_p, c_p, c_i64, c_p, c_i64, c_p]),
     "bgnn_gather_scale_bwd": (c_i32, [c_p, c_i64, c_p, c_i64, c_i32, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "bgnn_sag_score_bf16": (c_i32, [ctypes.POINTER(CsrStruct), c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_f32, c_p,
+                                    c_p, c_p]),
+    "bgnn_gather_scale_bf16": (c_i32, [c_p, c_i64, c_i32, c_p, c_p, c_i64, c_f32, c_p, c_i64, c_p]),
     "bgnn_filter_edges_ws_bytes": (c_sz, [c_i64]),
     "bgnn_filter_edges": (c_i32, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "bgnn_mlp2_supported": (c_i32, [c_i32, c_i32, c_i32]),

@@ -232,6 +232,12 @@ class BuckGNN(nn.Module):
         # before. Everywhere else (buckling, train mode, a hooked decoder, N < 1024, a decoder shape
         # node_head_bf16 declines, infer_bf16 off) the flag changes nothing. (_bf16_decoder_on)
         self.infer_bf16_decoder = False
+        # GraphSAGE_SAG where infer_bf16 is set (any truthy value) and its conditions hold: both layer
+        # loops on fused.sage_infer_layer and SAGPooling on the bf16 rows between them (the score in
+        # f32 from bgnn_sag_score_bf16, the kept rows by bgnn_gather_scale_bf16); loop 2's last layer
+        # writes f32 for the pooling and the decoder. Off: infer_bf16 leaves a SAG model on the f32
+        # path, as before. EAGNN_SAG and every other model: the flag changes nothing. (_sag_bf16_on)
+        self.infer_bf16_sag = False
         # GraphSAGE sum / mean models (and GraphSage_addAggr_Shared) on the fused layer loop, training
         # included: the operands of every N-row Linear product rounded to bf16 and z = x [W_l;W_r]^T
         # stored as bf16, as torch.autocast(bf16) would; accumulators, normalize, BatchNorm, skip,
@@ -354,6 +360,47 @@ class BuckGNN(nn.Module):
                     and self._fused_ok(x) and h % 8 == 0 and h <= 512
                     and (bns is None or all(bn.track_running_stats and bn.running_mean is not None
                                             for bn in bns)))
+
+    def _sag_bf16_on(self, x: Tensor) -> bool:
+        """Whether GraphSAGE_SAG takes its bf16 inference path (infer_bf16_sag): the flag beside a
+        truthy infer_bf16, _infer_bf16_on's own conditions for the sum aggregation over both
+        BatchNorm lists, and a pooling module bgnn_sag_score_bf16 restates: bgnn.nn.SAGPooling with a
+        one-channel bgnn.nn.SAGEConv scorer (sum aggregation, root weight, no projection, no
+        normalize), tanh and no min_score."""
+        if self.model_name != "GraphSAGE_SAG" or not getattr(self, "infer_bf16_sag", False) or not self.infer_bf16:
+            return False
+        if self.num_layers < 1 or not self._infer_bf16_on(x, "add", list(self.batch_norms_1) + list(self.batch_norms_2)):
+            return False
+        pool = self.pool
+        gnn = getattr(pool, "gnn", None)
+        return bool(isinstance(pool, SAGPooling) and isinstance(gnn, SAGEConv) and gnn.aggr in ("add", "sum")
+                    and not gnn.normalize and gnn.out_channels == 1 and gnn.root_weight and not gnn.project
+                    and pool.nonlinearity is torch.tanh and pool.min_score is None)
+
+    def _sag_forward_bf16(self, x: Tensor, edge_index: Tensor, edge_attr, batch: Optional[Tensor]):
+        """GraphSAGE_SAG's two layer loops and the pooling between them on bf16 rows (_sag_bf16_on):
+        fused.sage_infer_layer per layer -- eval dropout is the identity, so the skip after dropout
+        is the tail's skip: x_prev from the second layer of loop 1 on, and on every layer of loop 2 --
+        the score in f32 (pool.sag_score_bf16) and the kept rows in bf16 (pool.sag_pool_bf16). Loop
+        2's last layer writes f32. Returns (x, edge_index', edge_attr', batch')."""
+        from . import pool as P
+        graph = graph_for(edge_index, x.size(0))
+        for i, (conv, bn) in enumerate(zip(self.sage_layers_1, self.batch_norms_1)):
+            x = _fused.sage_infer_layer(x, _fused.infer_weights(conv), conv.lin_l.bias, _fused.bn_eval_coeffs(bn),
+                                        graph, 0, x_prev=x if i > 0 else None)
+        x = _fused._bf16_rows(x)   # (an empty loop 1: the encoder's f32 output, rounded to bf16 once)
+        if batch is None:
+            batch = torch.zeros(x.size(0), dtype=torch.long, device=x.device)
+        sp = self.pool
+        score = P.sag_score_bf16(x, sp.gnn, sp.select.weight, graph)
+        x, edge_index, edge_attr, batch, _perm, _score = P.sag_pool_bf16(x, score, sp.ratio, edge_index, edge_attr,
+                                                                         batch, sp.multiplier)
+        graph = graph_for(edge_index, x.size(0))
+        L2 = len(self.sage_layers_2)
+        for i, (conv, bn) in enumerate(zip(self.sage_layers_2, self.batch_norms_2)):
+            x = _fused.sage_infer_layer(x, _fused.infer_weights(conv), conv.lin_l.bias, _fused.bn_eval_coeffs(bn),
+                                        graph, 0, x_prev=x, out_f32=i == L2 - 1)
+        return x, edge_index, edge_attr, batch
 
     def _sage_bf16_on(self, x: Tensor, aggr: str) -> bool:
         """Whether the fused SAGE layer loop runs with autocast's rounding points (sage_bf16): the
@@ -550,9 +597,11 @@ class BuckGNN(nn.Module):
         # sage_bf16 keeps the encoder f32 and whole: folded, its last Linear would join layer 0's bf16
         # product (h and [W_l;W_r] W_in rounded instead of x0 and [W_l;W_r]: not autocast's points)
         unfold = sage_loop and self._sage_bf16_on(x, sage)
+        # GraphSAGE_SAG on bf16 rows (infer_bf16_sag): its first layer takes the encoder's f32 output too
+        sag16 = self._sag_bf16_on(x)
         # (GraphSAGE_SAG folds into sage_layers_1[0]: not when that list is empty, num_layers == 1)
         if (sage_loop or (name == "GraphSAGE_SAG" and len(self.sage_layers_1) >= 1)) and not infer and not unfold \
-                and self._sage_fused(x, sage) and sage != "max" and self._foldable_encoder(x):
+                and not sag16 and self._sage_fused(x, sage) and sage != "max" and self._foldable_encoder(x):
             x_in = self.node_encoder[-1]
             x, x_amax = mlp(self.node_encoder[:-1], x, return_amax=True)
         elif self._fused_ok(x) and x.size(0) >= 1024 and FUSED_ENCODER:
@@ -612,6 +661,8 @@ class BuckGNN(nn.Module):
             getattr(self, "sage_blocks_add")  # AttributeError, as in the reference (:405,473)
         elif name == "GraphSage_sumAggr_woBatchNorm":
             getattr(self, "sage_blocks_sum")  # AttributeError, as in the reference (:418)
+        elif name == "GraphSAGE_SAG" and sag16:
+            x, edge_index, edge_attr, batch = self._sag_forward_bf16(x, edge_index, edge_attr, batch)
         elif name == "GraphSAGE_SAG":   # Models/BuckGNN.py:493-511
             x = self._sag_sage_loop(x, edge_index, self.sage_layers_1, self.batch_norms_1, False, x_amax, x_in)
             x, edge_index, edge_attr, batch, _perm, _score = self.pool(x, edge_index, edge_attr, batch)

@@ -21,26 +21,42 @@ from .graph import prepare
 from .train import ColumnScaler, EigenvalueScaler, _denormalize_nodes, _node_criterion
 
 
+def _flags_set(model, flags: dict, run):
+    """run() with the model attributes `flags` set, each put back after (removed again where the
+    model did not carry it)."""
+    before = {k: vars(model)[k] for k in flags if k in vars(model)}
+    for k, v in flags.items():
+        setattr(model, k, v)
+    try:
+        return run()
+    finally:
+        for k in flags:
+            if k in before:
+                setattr(model, k, before[k])
+            else:
+                delattr(model, k)
+
+
+def _bf16_value(bf16):
+    return "all" if isinstance(bf16, str) and bf16 == "all" else bool(bf16)
+
+
 @torch.no_grad()
 def evaluate(model, batches: Iterable, normalizer: Optional[EigenvalueScaler] = None,
-             device=None, bf16=None) -> Dict[str, float]:
+             device=None, bf16=None, bf16_sag: Optional[bool] = None) -> Dict[str, float]:
     """Buckling-eigenvalue metrics of INFERENCE.py: mean / min / max APE in percent.
     bf16: None leaves the model's `infer_bf16` flag alone; True / False sets it for this call (the
     GraphSAGE sum / mean models' bf16 inference path, BuckGNN.infer_bf16) and restores it after;
-    "all" is passed through as it is (the max-aggregation model's bf16 path too)."""
+    "all" is passed through as it is (the max-aggregation model's bf16 path too).
+    bf16_sag: the same for `infer_bf16_sag` (GraphSAGE_SAG on bf16 rows where infer_bf16 is set):
+    None leaves it alone, True / False sets it for this call and restores it after."""
     model.eval()
-    if bf16 is None:
-        return _evaluate(model, batches, normalizer, device)
-    had = "infer_bf16" in vars(model)
-    before = getattr(model, "infer_bf16", False)
-    model.infer_bf16 = "all" if isinstance(bf16, str) and bf16 == "all" else bool(bf16)
-    try:
-        return _evaluate(model, batches, normalizer, device)
-    finally:
-        if had:
-            model.infer_bf16 = before
-        else:
-            del model.infer_bf16
+    flags = {}
+    if bf16 is not None:
+        flags["infer_bf16"] = _bf16_value(bf16)
+    if bf16_sag is not None:
+        flags["infer_bf16_sag"] = bool(bf16_sag)
+    return _flags_set(model, flags, lambda: _evaluate(model, batches, normalizer, device))
 
 
 def _evaluate(model, batches, normalizer, device) -> Dict[str, float]:
@@ -67,7 +83,8 @@ def _evaluate(model, batches, normalizer, device) -> Dict[str, float]:
 
 @torch.no_grad()
 def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, threshold: Optional[float] = None,
-                   device=None, bf16=None, return_predictions: bool = False) -> Dict[str, object]:
+                   device=None, bf16=None, return_predictions: bool = False,
+                   bf16_sag: Optional[bool] = None) -> Dict[str, object]:
     """The static heads' evaluation (INFERENCE.py:153-172,189-199; the validation loop of
     TRAIN_FINAL.py:349-384): eval mode, no_grad, per batch the model's prediction and its returned
     (super-node adjusted) batch vector, stress_errors of the denormalised values accumulated in a
@@ -80,25 +97,19 @@ def evaluate_nodes(model, batches: Iterable, normalizer=None, criterion=None, th
     bf16: None leaves the model's flags alone; True / "all" / False sets `infer_bf16` to that value
     and `infer_bf16_decoder` to its truth value for this call (the bf16 layer loop with the decoder
     on bf16 rows, BuckGNN.infer_bf16_decoder) and restores both after, as `evaluate` does.
+    bf16_sag: None leaves `infer_bf16_sag` alone; True / False sets it for this call and restores it
+    after (GraphSAGE_SAG on bf16 rows; the decoder there reads f32 rows either way).
     return_predictions: also return the fields, not only their metrics.
     Returns {"metrics_per_graph": sums / graphs, "metrics_per_batch": sums / batches, "graphs",
     "batches", "loss": the mean criterion value over batches or None}, and with return_predictions
     "predictions": one (denormalised prediction [n, C], returned batch vector) per batch."""
-    if bf16 is None:
-        return _evaluate_nodes(model, batches, normalizer, criterion, threshold, device, return_predictions)
-    flags = {"infer_bf16": "all" if isinstance(bf16, str) and bf16 == "all" else bool(bf16),
-             "infer_bf16_decoder": bool(bf16)}
-    before = {k: vars(model)[k] for k in flags if k in vars(model)}
-    for k, v in flags.items():
-        setattr(model, k, v)
-    try:
-        return _evaluate_nodes(model, batches, normalizer, criterion, threshold, device, return_predictions)
-    finally:
-        for k in flags:
-            if k in before:
-                setattr(model, k, before[k])
-            else:
-                delattr(model, k)
+    flags = {}
+    if bf16 is not None:
+        flags.update(infer_bf16=_bf16_value(bf16), infer_bf16_decoder=bool(bf16))
+    if bf16_sag is not None:
+        flags["infer_bf16_sag"] = bool(bf16_sag)
+    return _flags_set(model, flags, lambda: _evaluate_nodes(model, batches, normalizer, criterion, threshold, device,
+                                                            return_predictions))
 
 
 def _evaluate_nodes(model, batches, normalizer, criterion, threshold, device, return_predictions):

@@ -16,6 +16,10 @@ torch_geometric.nn.SAGPooling, as the reference builds it for GraphSAGE_SAG / EA
   to the score, which is how the scoring GNN trains).
 * `filter_edges` — bgnn_filter_edges (deterministic stream compaction); one host sync for
   the kept-edge count.
+* `sag_score_bf16`, `gather_scale_bf16`, `sag_pool_bf16` — the same step on bfloat16 rows for
+  eval-mode inference (BuckGNN.infer_bf16_sag): bgnn_sag_score_bf16 gives the float32 score,
+  topk_select and filter_edges run unchanged, bgnn_gather_scale_bf16 writes the kept rows. No
+  autograd.
 """
 from __future__ import annotations
 
@@ -149,6 +153,100 @@ def sag_pool(x: torch.Tensor, score: torch.Tensor, ratio: float, edge_index: tor
     xo = gather_scale(x, score, perm, new_id)
     if multiplier != 1:
         xo = multiplier * xo
+    ei, kept = filter_edges(edge_index, new_id, x.size(0))
+    ea = edge_attr.index_select(0, kept) if edge_attr is not None else None
+    return xo, ei, ea, batch_out, perm, score.reshape(-1)[perm]
+
+
+# ---------------------------------------------------------------------------
+# SAGPooling on bf16 rows (BuckGNN.infer_bf16_sag): eval mode only, no autograd.
+
+def _bf16_rows_checked(x: torch.Tensor, what: str) -> torch.Tensor:
+    if x.dtype != torch.bfloat16 or x.dim() != 2:
+        raise TypeError(f"{what}: x must be a bfloat16 [N, H] tensor")
+    H = x.size(1)
+    if H % 8 or not 8 <= H <= 512:
+        raise ValueError(f"{what}: needs H % 8 == 0 and 8 <= H <= 512 (got {H})")
+    # unit column stride, rows of whole 16-byte vectors (a column view of a wider buffer stays a view)
+    return x if (x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0) else x.contiguous()
+
+
+def _select_sign(conv, select_weight: torch.Tensor) -> float:
+    """sign(select.weight) as a host float, kept on the scorer module per weight version (as
+    fused._cached_weights keeps its matrices): one host read when the weight is first seen, written
+    in place or replaced, none per call. A zero weight gives NaN, as w / ||w|| does."""
+    key = (select_weight._version, select_weight.data_ptr(), str(select_weight.device))
+    hit = getattr(conv, "_bgnn_sag_sign", None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    if select_weight.numel() != 1:
+        raise ValueError("sag_score_bf16: select.weight must have one element (a one-channel scorer)")
+    w = float(select_weight.detach().reshape(-1)[0].item())
+    sgn = float("nan") if (w == 0 or w != w) else (1.0 if w > 0 else -1.0)
+    conv._bgnn_sag_sign = (key, sgn)
+    return sgn
+
+
+def _f32_vector(t: torch.Tensor, n: int, what: str) -> torch.Tensor:
+    t = t.detach().reshape(-1)
+    if t.dtype != torch.float32 or t.numel() != n:
+        raise TypeError(f"sag_score_bf16: {what} must hold {n} float32 value(s)")
+    return t.contiguous()
+
+
+@torch.no_grad()
+def sag_score_bf16(x: torch.Tensor, conv, select_weight: torch.Tensor, graph) -> torch.Tensor:
+    """SAGPooling's node score on bf16 rows (bgnn_sag_score_bf16, two launches, no host sync):
+    tanh(sign(w) * (sum_{j->i} <x_j, W_l> + b_l + <x_i, W_r>)) as float32 [N], for x bfloat16 [N, H],
+    `conv` the pooling's one-channel SAGEConv scorer (sum aggregation, its lin_l.weight, lin_l.bias
+    and lin_r.weight read as f32 [H] / scalar), `select_weight` the pooling's select.weight w and
+    `graph` the bgnn.graph.Graph of the edges. sign(w) is a host float cached per weight version
+    (_select_sign): no per-call host read. No autograd."""
+    require_cuda(x, select_weight, what="sag_score_bf16")
+    x = _bf16_rows_checked(x, "sag_score_bf16")
+    N, H = x.shape
+    if graph.fwd.n_rows != N:
+        raise ValueError(f"sag_score_bf16: the graph has {graph.fwd.n_rows} nodes, x {N} rows")
+    w_l = _f32_vector(conv.lin_l.weight, H, "lin_l.weight")
+    w_r = _f32_vector(conv.lin_r.weight, H, "lin_r.weight")
+    bias = _f32_vector(conv.lin_l.bias, 1, "lin_l.bias") if conv.lin_l.bias is not None else None
+    sgn = _select_sign(conv, select_weight)
+    score = torch.empty(N, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(N, 1), 2, dtype=torch.float32, device=x.device)
+    _lib.call("bgnn_sag_score_bf16", graph.fwd.ref(), x.data_ptr(), x.stride(0), N, H, w_l.data_ptr(),
+              w_r.data_ptr(), None if bias is None else bias.data_ptr(), sgn, score.data_ptr(), ws.data_ptr(),
+              _stream())
+    return score
+
+
+@torch.no_grad()
+def gather_scale_bf16(x: torch.Tensor, score: torch.Tensor, perm: torch.Tensor, multiplier: float = 1.0) -> torch.Tensor:
+    """((x[perm] * score[perm].view(-1, 1)) * multiplier) for bfloat16 rows x [N, H], as bfloat16
+    [K, H] (bgnn_gather_scale_bf16): both products in f32, each rounded, one bf16 rounding at the
+    store. score: float32 [N]; perm: int64 [K] (topk_select's). No autograd."""
+    require_cuda(x, score, perm, what="gather_scale_bf16")
+    x = _bf16_rows_checked(x, "gather_scale_bf16")
+    score = score.detach().reshape(-1).contiguous()
+    if score.dtype != torch.float32 or score.numel() != x.size(0):
+        raise TypeError("gather_scale_bf16: score must be float32 with one entry per row of x")
+    if perm.dtype != torch.long or perm.dim() != 1:
+        raise TypeError("gather_scale_bf16: perm must be an int64 vector (topk_select's output)")
+    perm = perm.contiguous()
+    K, H = perm.numel(), x.size(1)
+    out = torch.empty(K, H, dtype=torch.bfloat16, device=x.device)
+    _lib.call("bgnn_gather_scale_bf16", x.data_ptr(), x.stride(0), H, perm.data_ptr(), score.data_ptr(), K,
+              float(multiplier), out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
+@torch.no_grad()
+def sag_pool_bf16(x: torch.Tensor, score: torch.Tensor, ratio: float, edge_index: torch.Tensor,
+                  edge_attr: Optional[torch.Tensor], batch: torch.Tensor, multiplier: float = 1.0):
+    """sag_pool on bfloat16 rows: topk_select on the float32 score, gather_scale_bf16, filter_edges
+    (the same two host syncs). Returns (x' bfloat16, edge_index', edge_attr', batch', perm,
+    score[perm]). No autograd."""
+    perm, new_id, batch_out = topk_select(score, ratio, batch)
+    xo = gather_scale_bf16(x, score, perm, multiplier)
     ei, kept = filter_edges(edge_index, new_id, x.size(0))
     ea = edge_attr.index_select(0, kept) if edge_attr is not None else None
     return xo, ei, ea, batch_out, perm, score.reshape(-1)[perm]

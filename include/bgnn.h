@@ -893,6 +893,36 @@ int bgnn_filter_edges(const int64_t* edge_index, int64_t num_edges, const int32_
                       int64_t num_nodes, int64_t* out_edges, int64_t* kept, int64_t* n_kept,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* SAGPooling on bf16 rows (additive to ABI 22; BuckGNN.infer_bf16_sag). No atomics, every sum in a
+ * fixed order: bit-identical run to run.
+ *
+ * bgnn_sag_score_bf16: the score of SAGPooling(H, ratio, GNN=SAGEConv, aggr='add') for bf16 rows
+ *   x [N, H] (ldx), transform first, two launches and no host sync:
+ *     s_l[i] = <x_i, w_l>, s_r[i] = <x_i, w_r>                      w_l, w_r: f32 [H]
+ *     attn[i] = sum_{e in row i, CSR order} s_l[col[e]] + b + s_r[i]  b = bias[0], or 0 for NULL
+ *     score[i] = tanh(sgn * attn[i])                                  f32 [N]
+ *   Columns are widened to f32; products and sums are f32 (a row's dot product: 8 columns per lane in
+ *   column order, then the lanes of the row in a butterfly; a row of in-degree <= csr->chunk: CSR
+ *   order; a heavy row: lane l of a wave adds its edges l, l + 64, ..., then the butterfly). csr: the
+ *   forward CSR of the graph (n_rows == N; its heavy-row plan names the rows that take a wave; the
+ *   row-group plan and `ranges` are not used). ws: f32 [N, 2] scratch, 8-byte aligned.
+ *   BGNN_E_ARG, before anything is launched, when: N < 0; H % 8 != 0, H < 8 or H > 512; and with
+ *   N > 0: x, w_l, w_r, score, ws, csr or its rowptr is NULL; ldx < H or ldx % 8 != 0; x is not
+ *   16-byte aligned; csr->n_rows != N; heavy rows without heavy_row / chunk. N == 0 returns BGNN_OK
+ *   without a launch.
+ * bgnn_gather_scale_bf16: out[p, :] = bf16((f32(x[perm[p], :]) * score[perm[p]]) * multiplier) for
+ *   bf16 x [n, H] (ldx) and bf16 out [k, H] (ldo): two rounded f32 products in that order, one bf16
+ *   rounding (nearest even) at the store; perm / score as bgnn_topk_select leaves them.
+ *   BGNN_E_ARG, before anything is launched, when: k < 0; H % 8 != 0, H < 8 or H > 512; and with
+ *   k > 0: x, out, perm or score is NULL; ldx / ldo is < H or not a multiple of 8; x or out is not
+ *   16-byte aligned. k == 0 returns BGNN_OK without a launch. */
+int bgnn_sag_score_bf16(const bgnn_csr_t* csr, const void* x, int64_t ldx, int64_t N, int32_t H,
+                        const float* w_l, const float* w_r, const float* bias, float sgn,
+                        float* score, float* ws, void* stream);
+int bgnn_gather_scale_bf16(const void* x, int64_t ldx, int32_t H, const int64_t* perm,
+                           const float* score, int64_t k, float multiplier, void* out, int64_t ldo,
+                           void* stream);
+
 /* ------------------------------------------------------------------------
  * Node-encoder head (Models/BuckGNN.py:67-74, h >= 256): h = ReLU(ReLU(x W1^T + b1) W2^T + b2)
  * for x [N, F] (F = 16), W1 [D1, F] (D1 = 64), W2 [D2, D1] (D2 = 128), row-major fp32, on the
