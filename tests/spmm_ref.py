@@ -55,13 +55,39 @@ def tiny_edges(n):
 
 
 @functools.lru_cache(maxsize=None)
+def dense_edges():
+    """[2, E] int64, N = 600: the key batches of the row-group walker (tests/agg_b16_ref.py; not one of
+    KINDS). Rows 8..15 have in-degree 64 with disjoint sources (groups of 4: 256 keys, the group of 8:
+    512); rows 16..19 hold 64 distinct sources between them, rows 24..27 hold 65, rows 20..23 and
+    28..31 add a few repeats of those; row 40 is heavy (130 entries); the other rows below 560 draw 0..6
+    sources below 590; rows 560..599 are isolated and rows 590..599 are no edge's source."""
+    g = torch.Generator().manual_seed(600)
+    rows = {8 + t: list(range(64 * t, 64 * t + 64)) for t in range(8)}
+    rows.update({16: list(range(40)), 17: list(range(20, 64)), 18: list(range(5, 15)), 19: [],
+                 20: [0, 1], 21: [63, 7], 22: [], 23: [3, 3],
+                 24: list(range(100, 140)), 25: list(range(130, 165)), 26: list(range(100, 110)), 27: [],
+                 28: [101, 102], 29: [], 30: [], 31: [],
+                 40: torch.randint(0, 590, (130,), generator=g).tolist()})
+    for r in range(560):
+        if r not in rows:
+            rows[r] = torch.randint(0, 590, (int(torch.randint(0, 7, (1,), generator=g)),), generator=g).tolist()
+    src = torch.tensor([s for r in sorted(rows) for s in rows[r]], dtype=torch.int64)
+    dst = torch.tensor([r for r in sorted(rows) for _ in rows[r]], dtype=torch.int64)
+    ei = torch.stack([src, dst])
+    return ei[:, torch.randperm(ei.size(1), generator=g)]
+
+
+@functools.lru_cache(maxsize=None)
 def edges(kind):
     """(edge_index [2, E] int64, N, chunk) of a structure case. hand*: the hand graph of
     tests/test_gpu_spmm_b16.py (N = 1,003, isolated rows, duplicated edges, in-degree 64 / 65 / 700,
     a short last group), also rebuilt with chunk 4 / 16 / 200; hand_t: the hand graph reversed, so
     that the TRANSPOSE holds the rows of degree 64 / 65 / 700; store: a GraphStore batch (3 super
-    nodes, explicit group starts, ranges); tinyN: N rows."""
+    nodes, explicit group starts, ranges); tinyN: N rows; dense (dense_r8: the same graph, for a plan
+    of 8 rows per group): dense_edges, chunk 64."""
     from test_gpu_spmm_b16 import N_HAND, hand_edges, store_batch_host
+    if kind.startswith("dense"):
+        return dense_edges(), 600, 64
     if kind == "store":
         b = store_batch_host()
         return b.edge_index, int(b.num_nodes), 64
