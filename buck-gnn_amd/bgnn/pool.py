@@ -47,7 +47,11 @@ def _graph_offsets(batch: torch.Tensor) -> Tuple[torch.Tensor, int]:
 
 def topk_select(score: torch.Tensor, ratio: float, batch: torch.Tensor):
     """(perm [K] int64, new_id [N] int32 (-1 = dropped), batch' [K] int64): PyG's topk with
-    ties broken towards the lower node index (a stable descending sort)."""
+    ties broken towards the lower node index (a stable descending sort). The order is
+    torch.sort(descending=True, stable=True)'s: -0 == +0, and a NaN score (any sign, any payload)
+    ranks above +inf, NaNs being equal among themselves (lower node index first). So every slot
+    of `perm` is written and names a node of its graph, whatever the scores hold; a NaN score
+    is kept first and shows as NaN rows downstream."""
     require_cuda(score, batch, what="topk_select")
     score = score.detach().reshape(-1).contiguous()
     if score.dtype != torch.float32:

@@ -16,6 +16,14 @@
 // first; -0 == +0 as in torch.sort) with no workspace, no atomics, and O(n_g^2) compares
 // per graph — 2.5e7 for a 5,041-node mesh, microseconds on the chip.
 //
+// NaN scores: the order is torch.sort(descending=True, stable=True)'s total order. Every NaN
+// (any sign, any payload) ranks above +inf, NaNs are equal among themselves (ties: lower
+// node index first). With above(a, b) = a > b || (isnan(a) && !isnan(b)) the rank is
+// #{j > i : above(s_j, s_i)} + #{j < i : !above(s_i, s_j)}, so a graph's ranks are always a
+// permutation of 0 .. n_g - 1 and bgnn_topk_select fills every slot of perm. The kernel
+// turns each score into an int32 order key once (order_key: when it is staged and when s_i
+// is read) and compares keys, one compare per staged element.
+//
 // The edge filter is a deterministic three-pass stream compaction (per-block counts, one
 // scan block, ordered write), no atomics; kept edges keep edge_index order.
 #include "common.h"
@@ -26,34 +34,43 @@ namespace {
 
 constexpr int kRankTile = 2048;
 
+// int32 key with key(a) > key(b) iff a sorts before b in a descending torch.sort: the sign-magnitude
+// bits made two's complement (-0 and +0 both give 0), every NaN INT32_MAX (above +inf = 0x7F800000)
+__device__ __forceinline__ int32_t order_key(float s) {
+    const uint32_t u = __float_as_uint(s);
+    const uint32_t m = u & 0x7FFFFFFFu;
+    if (m > 0x7F800000u) return 0x7FFFFFFF;
+    return (u >> 31) ? -(int32_t)m : (int32_t)m;
+}
+
 __global__ __launch_bounds__(256) void k_topk_rank(const float* __restrict__ score,
                                                    const int64_t* __restrict__ batch,
                                                    const int64_t* __restrict__ ptr, int64_t N,
                                                    int32_t* __restrict__ rank) {
-    __shared__ __attribute__((aligned(16))) float tile[kRankTile];
+    __shared__ __attribute__((aligned(16))) int32_t tile[kRankTile];
     const int64_t i0 = (int64_t)blockIdx.x * 256;
     const int64_t i = i0 + threadIdx.x;
     const int64_t il = min(N, i0 + 256) - 1;
     const int64_t lo = ptr[batch[i0]], hi = ptr[batch[il] + 1];   // graphs this block touches
     const bool act = i < N;
     int64_t gs = 0, ge = 0;
-    float si = 0.f;
+    int32_t si = 0;
     if (act) {
         const int64_t g = batch[i];
         gs = ptr[g];
         ge = ptr[g + 1];
-        si = score[i];
+        si = order_key(score[i]);
     }
     int32_t r = 0;
     for (int64_t t = lo; t < hi; t += kRankTile) {
         const int n = (int)min((int64_t)kRankTile, hi - t);
         __syncthreads();
-        for (int k = threadIdx.x; k < n; k += 256) tile[k] = score[t + k];
+        for (int k = threadIdx.x; k < n; k += 256) tile[k] = order_key(score[t + k]);
         __syncthreads();
         if (!act) continue;
         const int a = (int)max((int64_t)0, gs - t), b = (int)min((int64_t)n, ge - t);
         const int own = (int)(i - t);   // position of i in this tile (may lie outside [a, b))
-        // j < i: s_j >= s_i counts; j >= i: s_j > s_i counts (j == i never does)
+        // on order keys: j < i: s_j >= s_i counts; j >= i: s_j > s_i counts (j == i never does)
         const int mid = min(max(own, a), b);
         for (int k = a; k < mid; ++k) r += tile[k] >= si ? 1 : 0;
         for (int k = mid; k < b; ++k) r += tile[k] > si ? 1 : 0;

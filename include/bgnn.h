@@ -867,7 +867,11 @@ int bgnn_readout_index(const int64_t* ptr, int32_t B, int64_t N, int64_t min_nod
  *
  * bgnn_topk_rank: rank[i] = position of node i in its graph's descending score order,
  *   #{j in graph(i) : s_j > s_i or (s_j == s_i and j < i)} (a stable descending sort;
- *   O(n_g^2) compares per graph, staged through LDS).
+ *   O(n_g^2) compares per graph, staged through LDS). The order is the total order of
+ *   torch.sort(descending=True, stable=True): -0 == +0; every NaN (any sign, any payload) ranks
+ *   above +inf, and NaNs are equal among themselves (ties: lower node index first) -- in the
+ *   formula, s_j > s_i reads "s_j > s_i or (s_j is NaN and s_i is not)" and s_j == s_i "neither
+ *   is above the other". A graph's ranks are therefore always a permutation of 0 .. n_g - 1.
  * bgnn_topk_select: node i is kept iff rank[i] < k[g] (k[g] = ceil(ratio * n_g), computed by
  *   the caller in fp32 as PyG does); perm[new_ptr[g] + rank[i]] = i, new_id[i] = that position
  *   or -1, batch_out[position] = g (optional). new_ptr [B+1] = running sums of k.

@@ -1,6 +1,6 @@
 """The window machinery of the GPU conformance matrices (tests/test_gpu_sage_rows_matrix.py,
-tests/test_gpu_spmm_matrix.py, tests/test_gpu_dense_matrix.py, tests/test_gpu_gemm_b16_matrix.py): outputs as NaN-filled windows inside guarded allocations,
-inputs with NaN after their last row, the comparison against an fp64 reference under a per-element bound
+tests/test_gpu_spmm_matrix.py, tests/test_gpu_dense_matrix.py, tests/test_gpu_gemm_b16_matrix.py, tests/test_gpu_pool_matrix.py): outputs as NaN-filled windows inside guarded allocations
+(integer outputs: sentinel-filled windows, IntWin), inputs with NaN after their last row, the comparison against an fp64 reference under a per-element bound
 with the largest err / bound kept per section, and the amax check."""
 import torch
 
@@ -130,6 +130,45 @@ class Win:
         assert bad.numel() == 0, (f"{label}: {bad.numel()} guard elements outside the {self.rows} x {self.cols} "
                                   f"{self.dtype} window (ld {self.ld}) overwritten; first at flat offset {int(bad[0])}, "
                                   f"window at {int(self.idx[0, 0]) if self.idx.numel() else 0}")
+
+
+class IntWin:
+    """A window of n int32 / int64 / uint8 elements pre-filled with a sentinel no valid result can equal
+    (-0x5EED; 0xA5 for uint8), inside an allocation whose `pad` guard elements on either side hold a second
+    pattern (PATTERN, PATTERN twice, 0x5A). pad is a multiple of 64 elements, so the window starts as
+    aligned as the allocation (a workspace: at least 64 bytes)."""
+    SENTINEL = {torch.int32: -0x5EED, torch.int64: -0x5EED, torch.uint8: 0xA5}
+    GUARD = {torch.int32: PATTERN, torch.int64: PATTERN << 32 | PATTERN, torch.uint8: 0x5A}
+
+    def __init__(self, dev, n, dtype=torch.int32, pad=64):
+        assert pad % 64 == 0 and pad > 0
+        self.n, self.pad, self.dtype = n, pad, dtype
+        self.sentinel, self.pattern = self.SENTINEL[dtype], self.GUARD[dtype]
+        self.buf = torch.full((n + 2 * pad,), self.pattern, dtype=dtype, device=dev)
+        self.buf[pad:pad + n] = self.sentinel
+        self.ptr = self.buf.data_ptr() + pad * self.buf.element_size()
+
+    def read(self):
+        return self.buf[self.pad:self.pad + self.n].cpu()
+
+    def guard(self, label):
+        g = torch.cat([self.buf[:self.pad], self.buf[self.pad + self.n:]])
+        bad = (g != self.pattern).nonzero().flatten()
+        assert bad.numel() == 0, (f"{label}: {bad.numel()} guard elements around the {self.n}-element {self.dtype} "
+                                  f"window overwritten; first at {int(bad[0]) - self.pad if int(bad[0]) < self.pad else int(bad[0]) - self.pad + self.n} "
+                                  f"relative to the window's start")
+
+    def assert_all_written(self, label, upto=None):
+        """no sentinel is left in the first `upto` (default: all n) elements"""
+        upto = self.n if upto is None else upto
+        left = (self.read()[:upto] == self.sentinel).nonzero().flatten()
+        assert left.numel() == 0, f"{label}: {left.numel()} of the first {upto} elements never written; first at {int(left[0])}"
+
+    def assert_untouched(self, label, start=0):
+        """the elements from `start` on still hold the sentinel"""
+        hit = (self.read()[start:] != self.sentinel).nonzero().flatten()
+        assert hit.numel() == 0, (f"{label}: {hit.numel()} elements behind the first {start} of the {self.n}-element window "
+                                  f"written; first at {start + int(hit[0])}")
 
 
 class Buf:

@@ -6,6 +6,7 @@ import torch
 import bgnn
 from bgnn.graph import Graph, SegmentIndex, make_plan
 from bgnn import synthetic as S
+from pool_ref import np_groups   # the host restatement of bgnn_group_plan's rule
 
 pytestmark = pytest.mark.gpu
 
@@ -15,39 +16,6 @@ def np_csr(keys, vals, n):
     rowptr = np.zeros(n + 1, dtype=np.int64)
     np.add.at(rowptr, keys + 1, 1)
     return np.cumsum(rowptr), vals[order], order
-
-
-def np_groups(rowptr, col, n, chunk, R, grow=None):
-    """Host restatement of bgnn_group_plan's rule (include/bgnn.h): per group of at most R rows
-    (rows [g*R, g*R+R), or [grow[g], grow[g+1])), the light rows' entries keyed by (source,
-    occurrence within the row), numbered by first appearance, with the mask of the rows holding
-    each key."""
-    if grow is None:
-        grow = list(range(0, n, R)) + [n]
-    G = len(grow) - 1
-    gsrc, gmask, gcnt = {}, {}, np.zeros(G, dtype=np.int64)
-    for g in range(G):
-        keys, src, mask = {}, [], []
-        for t in range(grow[g + 1] - grow[g]):
-            r = grow[g] + t
-            b, e = int(rowptr[r]), int(rowptr[r + 1])
-            if e - b > chunk:
-                continue
-            occ = {}
-            for q in range(b, e):
-                s_ = int(col[q])
-                k = (s_, occ.get(s_, 0))
-                occ[s_] = k[1] + 1
-                if k not in keys:
-                    keys[k] = len(src)
-                    src.append(s_)
-                    mask.append(0)
-                mask[keys[k]] |= 1 << t
-        base = int(rowptr[grow[g]])
-        for i, (s_, m) in enumerate(zip(src, mask)):
-            gsrc[base + i], gmask[base + i] = s_, m
-        gcnt[g] = len(src)
-    return gsrc, gmask, gcnt
 
 
 def check_groups(csr, n, chunk):
